@@ -20,7 +20,20 @@ by one rank, the 2 % sampled slices are all-gathered, the control loop runs repl
 samples, a merge and the encodes of its results run on the rank that owns the node, RCCL on
 device buffers.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0: the headline (`value`, `ms_per_step`), the configuration, the SPSS
+figures and phase times of the last timed build.  A plain run does only that: set-up, warm-up, the
+timed builds, and the outputs if --dump-outputs is given.
+
+  --dump-outputs DIR  after the timed builds, what the last one computed -- the KmerSetSet a caller
+               receives -- as DIR/<name>.npy (float64, float32 for the improvements): the merge
+               sequence (`iterations`, `checkpoints`, `improvements`), per node its k-mer count,
+               XOR hash (two 32-bit halves) and SPSS shape (strings, bases), and a fixed, seeded
+               sample of every node's SPSS (`spss_bases`: 2-bit codes, -1 past the end;
+               `spss_lengths`: string lengths - k).  Same arguments, same inputs, same files.
+
+--full adds what takes work of its own beyond the headline, in the same process, after the timed builds
+(each block stays null in a plain run; --no-verify / --no-pair-merge / --no-cpu-baseline leave one out):
+  verified     Size and XOR Hash of every Get(i) against the decoded input.
   roofline     the loop's dominant stage, the neighbour probe of the SPSS encode (the rc partition,
                k_adj_rc1 and k_adj_fwd_targets; one timed "launch" = the stage of one encode):
                algorithmic bytes = 5.3 B per k-mer (read key + write adjacency byte
@@ -91,6 +104,82 @@ def host_cores():
     return n
 
 
+DUMP_SEED = 20240917            # fixes which windows of every node's SPSS --dump-outputs samples
+DUMP_WINDOWS = 4                # windows per node, of packed words and of string lengths
+DUMP_SAMPLE_BYTES = 40 << 20    # budget of the SPSS sample (spss_bases + spss_lengths), whatever the node count
+
+
+def dump_outputs(out_dir, ctx, kss, owned, rank, it, cp, imp):
+    """--dump-outputs: what the last timed build computed, as float arrays under out_dir (module docstring).
+    Every rank of an owned build must call it (node_table is collective); rank 0 writes."""
+    import ctypes as C
+
+    import numpy as np
+
+    from kmersets import capi
+
+    L, n = capi.lib(), kss.size()
+    if owned:
+        table = kss.node_table()                         # (size, XOR hash as int64) from the ranks holding them
+        sizes, hashes = table[:, 0], table[:, 1].astype(np.uint64)
+    if rank != 0:
+        return
+    if not owned:
+        sizes, hashes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint64)
+    words_per_window = int(min(128, max(1, DUMP_SAMPLE_BYTES // max(n, 1) // DUMP_WINDOWS // (32 * 4 + 2 * 8))))
+    lens_per_window = 2 * words_per_window
+    bases = np.full((n, DUMP_WINDOWS * words_per_window * 32), -1.0, dtype=np.float32)
+    lens = np.full((n, DUMP_WINDOWS * lens_per_window), -1.0, dtype=np.float64)
+    shape = np.zeros((n, 2), dtype=np.float64)           # strings, bases
+    shifts = np.uint64(62) - np.uint64(2) * np.arange(32, dtype=np.uint64)
+
+    def window_starts(i, kind, n_items, width):
+        rng = np.random.default_rng([DUMP_SEED, i, kind])
+        return np.sort(rng.integers(0, max(n_items - width, 0) + 1, DUMP_WINDOWS))
+
+    for i in range(n):
+        holder = kss.node_holder(i)
+        if holder not in (-1, rank):
+            shape[i] = -1                                # this node's SPSS lives on another rank
+            continue
+        sv, sz = capi.SpssView(), C.c_int64()
+        if owned:
+            capi.check(L.ksh_kss_node(kss.h, i, C.byref(sv), None, C.byref(sz)))
+        else:
+            v, h = capi.SetView(), C.c_uint64()
+            capi.check(L.ksh_kss_node(kss.h, i, C.byref(sv), C.byref(v), C.byref(sz)))
+            capi.check(L.ksh_set_hash(ctx.h, C.byref(kss.g), C.byref(v), C.byref(h)))
+            sizes[i], hashes[i] = sz.value, h.value
+        shape[i] = (sv.n_strings, sv.n_bases)
+        n_words = (sv.n_bases + 31) // 32
+        for w, s in enumerate(window_starts(i, 0, n_words, words_per_window)):
+            m = int(min(words_per_window, n_words - s))
+            if m <= 0:
+                continue
+            buf = np.zeros(m, dtype=np.uint64)
+            capi.check(L.ksh_ctx_memcpy_d2h(ctx.h, buf.ctypes.data_as(C.c_void_p), C.c_void_p(sv.d_words + 8 * int(s)), 8 * m))
+            codes = ((buf[:, None] >> shifts[None, :]) & np.uint64(3)).reshape(-1).astype(np.float32)
+            codes[np.arange(codes.size) + 32 * int(s) >= sv.n_bases] = -1.0
+            at = w * words_per_window * 32
+            bases[i, at:at + codes.size] = codes
+        for w, s in enumerate(window_starts(i, 1, sv.n_strings, lens_per_window)):
+            m = int(min(lens_per_window, sv.n_strings - s))
+            if m <= 0:
+                continue
+            buf = np.zeros(m, dtype=np.uint32)
+            capi.check(L.ksh_ctx_memcpy_d2h(ctx.h, buf.ctypes.data_as(C.c_void_p), C.c_void_p(sv.d_lens + 4 * int(s)), 4 * m))
+            lens[i, w * lens_per_window:w * lens_per_window + m] = buf
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "iterations": it.astype(np.float64), "checkpoints": cp.astype(np.float64), "improvements": imp.astype(np.float32),
+        "node_sizes": sizes.astype(np.float64),
+        "node_hashes": np.stack([hashes >> np.uint64(32), hashes & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64),
+        "node_spss_shape": shape, "spss_bases": bases, "spss_lengths": lens,
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -121,7 +210,15 @@ def main():
     ap.add_argument("--dump-trace", default="",
                     help="write the last build's merge sequence, node sizes and phase times to this file "
                          "(input of tools/owned_schedule.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed builds, also the blocks that take work of their own: verified, roofline "
+                         "(HIP-event timers in the timed builds and one more build on one stream), pair_merge, "
+                         "cpu_baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed build computed to DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -207,8 +304,9 @@ def main():
         if first_wall is None:
             first_wall = time.perf_counter() - w0
         warm.close()
-    ctx.enable_timing(1)
-    ctx.timing_reset()
+    if args.full:
+        ctx.enable_timing(1)
+        ctx.timing_reset()
     fence()
     t0 = time.perf_counter()
     kss = None
@@ -219,17 +317,20 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     KINDS = (("k_adjacency", 3), ("ranking_walks", 4), ("emit_walks", 5))
-    timers = {name: (ctx.timing_read(kind), ctx.timing_units(kind), ctx.timing_wall(kind)) for name, kind in KINDS}
-    ctx.enable_timing(False)
+    if args.full:
+        timers = {name: (ctx.timing_read(kind), ctx.timing_units(kind), ctx.timing_wall(kind)) for name, kind in KINDS}
+        ctx.enable_timing(False)
     # The roofline leg proper: ONE more build of the same inputs on ONE stream (lanes = 1), every launch of the
     # stage bracketed by HIP events on that stream.  In the timed region above several encodes share the GPU
     # (lanes): a launch's duration there depends on whose kernels run beside it, so it says how the streams
     # overlap, not what the kernel does with the GPU; both are reported (`roofline.timed_region`).
     lanes_used = args.lanes if args.lanes > 0 else int(os.environ.get("KSH_LANES", "4"))
-    timers_timed, excl_wall = timers, None
+    timers_timed, excl_wall = (timers if args.full else None), None
     st = kss.stats()                 # (of the last TIMED build: phases, encode counts, SPSS sizes)
     it, cp, imp = kss.trace()
-    if not owned and lanes_used != 1:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, kss, owned, rank, it, cp, imp)
+    if args.full and not owned and lanes_used != 1:
         kss.close()
         ctx.set_lanes(1)
         ctx.enable_timing(1)
@@ -290,7 +391,7 @@ def main():
                   open(args.dump_trace, "w"))
 
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         # the reference's own --check (src/kmerset-multiple-compress.cc:104-126) on the device: Size
         # and XOR Hash of Get(i) against the decoded input, every i (every rank checks the sets it owns)
         bad, checked = [], 0
@@ -333,7 +434,7 @@ def main():
 
     # ---- pair-merge block (configs[1]; the round-1 headline, kept as an extra key)
     pair_merge = None
-    if rank == 0 and not owned and not args.no_pair_merge:
+    if args.full and rank == 0 and not owned and not args.no_pair_merge:
         kss.close()
         kss = None
         pm_sets = [synth_torch.device_set(g, km) for km in synth_torch.phylogeny_sets(k, 4, int(1e7), 2, dev)]
@@ -369,7 +470,7 @@ def main():
 
     # ---- CPU baseline: the oracle's port of the loop, threads as the reference has them
     cpu_baseline = None
-    if rank == 0 and not owned and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not owned and not args.no_cpu_baseline:
         # the copy that is timed is compiled here, on the host it runs on, with the reference's release
         # flags (CMakeLists.txt:5); the portable build the tests load is the fall-back
         import subprocess
@@ -449,7 +550,7 @@ def main():
 
     traffic, traffic_src = None, None
     pmc_file = os.path.join(ROOT, "profiles", "pmc_adjacency.json")
-    if rank == 0 and os.path.exists(pmc_file):
+    if args.full and rank == 0 and os.path.exists(pmc_file):
         pmc = json.load(open(pmc_file))
         if pmc.get("k") == k and pmc.get("bytes_per_kmer"):
             traffic_per_kmer = pmc["bytes_per_kmer"]
@@ -459,7 +560,8 @@ def main():
     else:
         traffic_per_kmer = None
 
-    if rank == 0:
+    roofline = None
+    if args.full and rank == 0:
         # `timers`: the one-stream build (the stage's launches alone on the GPU: sum of spans == their union);
         # `timers_timed`: the timed region, where launches of different lanes overlap -- stream time = the sum of
         # the spans (what a kernel trace's per-kernel durations add up to), union = the time during which the
@@ -489,6 +591,34 @@ def main():
             other[name] = {"ms_total": ms, "launches": n, "ns_per_kmer": ms * 1e6 / max(units, 1),
                            "timed_region_ns_per_kmer_stream_time": tms * 1e6 / max(tunits, 1),
                            "timed_region_ns_per_kmer_union": twall * 1e6 / max(tunits, 1)}
+        roofline = {
+            "bound": "hbm",
+            "kernel": "neighbour-probe stage of the SPSS encode (k_rc_hist / k_rc_columns / k_rc_scatter_l1+l2 / k_rc_bounds / "
+                      "k_adj_rc1 (k_adj_rc for groups whose records do not fit it) / k_tgt_bounds / k_tgt_split / k_tgt_subcuts / k_adj_fwd_targets; the in-place k_adjacency for sets outside their range): "
+                      "one timed launch = the whole stage of one encode",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "launches": int(adj_launches),
+            "avg_launch_ms": avg_launch_ms,
+            "timing": "HIP events on the context's stream around every launch of the stage, in one build of the "
+                      "same inputs on ONE stream (lanes = 1) run right after the timed builds%s"
+                      % ("" if excl_wall is None else ": %.1f ms for that build" % (excl_wall * 1e3)),
+            "kmers_per_launch": kmers_per_launch,
+            "ns_per_kmer": adj_ms * 1e6 / max(adj_units, 1),
+            "timed_region": timed_region,
+            "algorithmic_bytes_per_kmer": ENCODE_BYTES_PER_KMER,
+            "algorithmic_bytes_per_launch": bytes_per_launch,
+            "probe_inclusive_bytes_per_kmer": ENCODE_PROBE_BYTES_PER_KMER,
+            "probe_inclusive_frac": achieved / HBM_PEAK_GBS * ENCODE_PROBE_BYTES_PER_KMER / ENCODE_BYTES_PER_KMER,
+            "share_of_one_stream_build": adj_ms * 1e-3 / (excl_wall if excl_wall else elapsed / args.steps),
+            "other_kernels": other,
+        }
+
+    if rank == 0:
         out = {
             "metric": "Mk-mers/s processed in kmerset-multiple-compress; bytes/k-mer after SPSS",
             "value": value,
@@ -496,6 +626,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong" if world > 1 else "weak",
@@ -518,32 +649,7 @@ def main():
             },
             "phase_seconds_last_build": st["phase_seconds"],
             "phase_seconds_one_stream_build": phase_seconds_one_stream,
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "neighbour-probe stage of the SPSS encode (k_rc_hist / k_rc_columns / k_rc_scatter_l1+l2 / k_rc_bounds / "
-                          "k_adj_rc1 (k_adj_rc for groups whose records do not fit it) / k_tgt_bounds / k_tgt_split / k_tgt_subcuts / k_adj_fwd_targets; the in-place k_adjacency for sets outside their range): "
-                          "one timed launch = the whole stage of one encode",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "launches": int(adj_launches),
-                "avg_launch_ms": avg_launch_ms,
-                "timing": "HIP events on the context's stream around every launch of the stage, in one build of the "
-                          "same inputs on ONE stream (lanes = 1) run right after the timed builds%s"
-                          % ("" if excl_wall is None else ": %.1f ms for that build" % (excl_wall * 1e3)),
-                "kmers_per_launch": kmers_per_launch,
-                "ns_per_kmer": adj_ms * 1e6 / max(adj_units, 1),
-                "timed_region": timed_region,
-                "algorithmic_bytes_per_kmer": ENCODE_BYTES_PER_KMER,
-                "algorithmic_bytes_per_launch": bytes_per_launch,
-                "probe_inclusive_bytes_per_kmer": ENCODE_PROBE_BYTES_PER_KMER,
-                "probe_inclusive_frac": achieved / HBM_PEAK_GBS * ENCODE_PROBE_BYTES_PER_KMER / ENCODE_BYTES_PER_KMER,
-                "share_of_one_stream_build": adj_ms * 1e-3 / (excl_wall if excl_wall else elapsed / args.steps),
-                "other_kernels": other,
-            },
+            "roofline": roofline,
             "cpu_baseline": cpu_baseline,
             "spss": spss,
             "verified": verified,

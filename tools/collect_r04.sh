@@ -14,10 +14,10 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/${KSH_ROUND:-r04}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --dump-trace $O/${TAG}_trace.json "$@" > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 $R/bench.py --full --dump-trace $O/${TAG}_trace.json "$@" > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 cut -c1-700 $O/${TAG}_bench.json; echo
 for L in 1 4; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats_l$L -o stats -- python3 $R/bench.py --steps 1 --warmup 1 --lanes $L --no-cpu-baseline --no-verify --no-pair-merge > $O/${TAG}_bench_under_rocprof_l$L.json 2> $O/${TAG}_rocprof_stats_l$L.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats_l$L -o stats -- python3 $R/bench.py --full --steps 1 --warmup 1 --lanes $L --no-cpu-baseline --no-verify --no-pair-merge > $O/${TAG}_bench_under_rocprof_l$L.json 2> $O/${TAG}_rocprof_stats_l$L.err
   T="$(find $O/${TAG}_stats_l$L -name '*kernel_trace.csv' | head -1)"
   python3 $R/tools/gpu_gaps.py "$T" > $O/${TAG}_gaps_l$L.txt
   python3 $R/tools/lane_overlap.py "$T" -2 > $O/${TAG}_overlap_l$L.txt   # (the timed build; the last one is the one-stream roofline leg)
@@ -25,9 +25,9 @@ for L in 1 4; do
   rm -rf $O/${TAG}_stats_l$L
   echo stats l$L done
 done
-rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $O/${TAG}_pmc_fetch -o fetch -- python3 $R/bench.py --sets 16 --steps 1 --warmup 0 --lanes 1 --no-cpu-baseline --no-verify --no-pair-merge > $O/${TAG}_pmc_fetch.json 2> $O/${TAG}_pmc_fetch.err
+rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $O/${TAG}_pmc_fetch -o fetch -- python3 $R/bench.py --full --sets 16 --steps 1 --warmup 0 --lanes 1 --no-cpu-baseline --no-verify --no-pair-merge > $O/${TAG}_pmc_fetch.json 2> $O/${TAG}_pmc_fetch.err
 echo fetch done
-rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $O/${TAG}_pmc_write -o write -- python3 $R/bench.py --sets 16 --steps 1 --warmup 0 --lanes 1 --no-cpu-baseline --no-verify --no-pair-merge > $O/${TAG}_pmc_write.json 2> $O/${TAG}_pmc_write.err
+rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $O/${TAG}_pmc_write -o write -- python3 $R/bench.py --full --sets 16 --steps 1 --warmup 0 --lanes 1 --no-cpu-baseline --no-verify --no-pair-merge > $O/${TAG}_pmc_write.json 2> $O/${TAG}_pmc_write.err
 echo write done
 F=$(find $O/${TAG}_pmc_fetch -name "*counter_collection.csv" | head -1)
 W=$(find $O/${TAG}_pmc_write -name "*counter_collection.csv" | head -1)
