@@ -332,6 +332,44 @@ int ksh_spss_encode_routes(ksh_ctx* ctx, int64_t* routes);
 /* Frees the current plan's device memory (also done by the next plan / ctx_destroy). */
 int ksh_spss_encode_release(ksh_ctx* ctx);
 
+/* ---- SPSS path cover from caller-supplied unitigs -------------------------------------------
+ * GetSPSSCanonical(unitigs, prefixes, suffixes, fast, n_workers, n_buckets) (lib/core/spss.h:1039-1829)
+ * and GetSPSS(unitigs, prefixes, n_workers, n_buckets) (:697-1014): the n strings of `unitigs`
+ * (ksh_spss_view layout, e.g. what ksh_spss_encode_write with mode 1, ksh_spss_from_text_write or
+ * ksh_fasta_write produce) are the nodes, in the order given; the prefix / suffix maps of the
+ * reference are derived on the device.  The output strings and their order are the oracle's
+ * (reference n_workers == 1): canonical != 0 with fast != 0 is the greedy path cover of
+ * GetSPSSCanonical(fast = true), fast == 0 the one-thread path extension of fast = false;
+ * canonical == 0 is GetSPSS (`fast` is ignored).
+ * Edges come from the strings' end k-mers only, taken as they are (P = first, S = last k-mer):
+ * the right side of i meets j != i where P_j == Next(S_i, c) or S_j == rc(Next(S_i, c)), the
+ * left side where S_j == Prev(P_i, c) or P_j == rc(Prev(P_i, c)); non-canonical: only
+ * P_j == Next(S_i, c).  Interior k-mers are not looked at (neither does the reference): a k-mer
+ * that occurs in two strings is not detected.
+ * Preconditions, checked on the device, each a KSH_INVALID_ARGUMENT that names it and the string:
+ *   canonical: the canonical forms of the end k-mers are pairwise distinct across strings (a
+ *     string given twice, or together with its reverse complement, is refused); a string whose
+ *     first and last k-mers have the same canonical form must be exactly K long; no end k-mer
+ *     is its own reverse complement (even k only, as the encode refuses such a set);
+ *   non-canonical: the first k-mers are pairwise distinct, and so are the last k-mers;
+ *   both: sum(lens + K) == n_bases.
+ * Every unitig set of a k-mer set satisfies them (GetUnitigs / GetUnitigsCanonical, or the
+ * unitigs of a compacted de Bruijn graph tool), in any order and orientation.
+ * Limits: at most 2^30 - 1 strings (the path cover's walk records hold 31-bit state ids) and
+ * fewer than 2^31 - 16 k-mers in all.  An empty input gives 0 strings and 0 bases.
+ * The cover plan takes the encode plan's slot: a new plan of either kind replaces the current
+ * one, ksh_spss_encode_write / _routes refuse a cover plan and ksh_spss_cover_write / _stats an
+ * encode plan.  The input must stay alive and unchanged until ksh_spss_cover_write.
+ * plan : edge table, path cover, string layout; returns the output's sizes.
+ * write: d_words = ceil(n_bases / 32) words, d_lens = n_strings values (len - K). */
+int ksh_spss_cover_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* unitigs, int canonical, int fast,
+                        int64_t* n_strings, int64_t* n_bases);
+int ksh_spss_cover_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens);
+/* stats = { unitigs (input strings), matching rounds, strings, bases } of the current cover plan. */
+int ksh_spss_cover_stats(ksh_ctx* ctx, int64_t stats[4]);
+/* Frees the current plan (of either kind), as ksh_spss_encode_release does. */
+int ksh_spss_cover_release(ksh_ctx* ctx);
+
 /* ---- KmerSetSet: the loop kmerset-multiple-compress runs -------------------------------
  * ksh_kss_build = KmerSetSet(vector<KmerSetCompact>, canonical, n_workers)
  * (lib/core/kmer_set_set.h:109-427) on device-resident sets.  inputs are the

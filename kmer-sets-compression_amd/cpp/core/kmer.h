@@ -10,6 +10,7 @@
 #include <cassert>
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <string>
 
 template <int K>
@@ -85,5 +86,14 @@ template <int K>
 bool operator<(const Kmer<K>& l, const Kmer<K>& r) { return l.Bits() < r.Bits(); }
 template <int K>
 bool operator>(const Kmer<K>& l, const Kmer<K>& r) { return l.Bits() > r.Bits(); }
+
+// (the key of GetPrefixesFromUnitigs / GetSuffixesFromUnitigs' maps; the reference hashes Kmer::Hash through
+// AbslHashValue, kmer.h:231-234)
+namespace std {
+template <int K>
+struct hash<Kmer<K>> {
+  std::size_t operator()(const Kmer<K>& x) const noexcept { return x.Hash(); }
+};
+}  // namespace std
 
 #endif

@@ -3570,6 +3570,11 @@ struct EncPlan {
   const uint32_t* ends = nullptr;  // the end k-mers, ascending (aliases pos)
   int64_t n_ends = 0;
   WalkLog log_rulers{}, log_heads{};  // hdr == NULL: the strings are written by walking (k_emit_rulers / k_emit_heads)
+  // a cover plan (ksh_spss_cover_plan): the caller's strings are the unitigs, n = n_u of them
+  bool cover = false;
+  ksh_spss_view in{};
+  int64_t* in_start = nullptr;  // base offset of every input string
+  bool cover_ready = false;     // the plan ran to its end: the write may read its arrays
 };
 
 inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
@@ -3680,6 +3685,78 @@ size_t encode_scratch_bytes(const ksh_geom* g, int64_t n) {
 int encode_reserve(ksh_ctx* ctx, const ksh_geom* g, int64_t n) {
   KSH_TRY(slot_reserve(ctx, kSlotEncode, enc_slot_bytes(g, n)));
   return arena_reserve(ctx, enc_arena_bytes(g, n));
+}
+
+// The unitig-level stage of the path cover, shared by the encode (modes 0 and 2) and ksh_spss_cover_*: from the
+// edge table (edges, mate as k_edges leaves them) and u_len of n_u unitigs to every unitig's string, place in it
+// and orientation (u_sid, u_koff, u_flip), the strings' k-mer counts - 1 (lens) and their lengths in bases
+// (str_start, not yet scanned).  Enqueued on the context's stream; reads the matching's flags back once per batch.
+static int cover_stage(ksh_ctx* ctx, EncPlan* p, int64_t n_u, bool directed, bool slow, int k, int* walk_rounds_out) {
+  hipStream_t st = ctx->stream;
+  EncCtl* ctl = p->ctl;
+  int walk_rounds = 0;
+  p->rounds = 0;
+  if (slow) {
+    hipLaunchKernelGGL(k_match_slow, dim3(1), dim3(64), 0, st, p->edges, p->mate, n_u);
+  } else {
+    // rounds in batches, one look at the flags per batch: four rounds first (every round past the last one that
+    // found something is two launches that return at once, some 9 us each), then eight at a time
+    for (bool more = true; more;) {
+      if (p->rounds) KSH_HIP(hipMemsetAsync(ctl->match_live, 0, sizeof(ctl->match_live), st));
+      const int batch = p->rounds ? kMatchBatch : kMatchFirst;
+      for (int r = 0; r < batch; r++) {
+        hipLaunchKernelGGL(k_match_best, dim3(nblk(2 * n_u)), dim3(256), 0, st, p->edges, p->mate, 2 * n_u, directed,
+                           p->best_prio, p->best_w, r ? &ctl->match_live[r - 1] : nullptr, &ctl->match_live[r]);
+        hipLaunchKernelGGL(k_match_commit, dim3(nblk(2 * n_u)), dim3(256), 0, st, p->best_prio, p->best_w, 2 * n_u,
+                           &ctl->match_live[r], p->mate);
+      }
+      KSH_HIP(hipMemcpyAsync(ctx->h_pinned, ctl->match_live, batch * sizeof(int), hipMemcpyDeviceToHost, st));
+      KSH_HIP(hipStreamSynchronize(st));
+      const int* live = reinterpret_cast<const int*>(ctx->h_pinned);
+      int ran = 0;
+      while (ran < batch && live[ran]) ran++;
+      more = ran == batch;
+      p->rounds += more ? batch : ran + 1;  // (the round that found nothing counts, as before)
+      if (p->rounds > 100000) return fail(KSH_INTERNAL, "matching did not converge");
+    }
+    // the path extension of fast = false never closes a loop; the greedy matching can:
+    // components of the chosen edges (parallel union-find), the ones without a terminal are loops
+    DevDsu dsu{reinterpret_cast<unsigned long long*>(p->sc01)};  // sc01 is only filled by k_string_counts
+    uint8_t* has_terminal = p->scls;                             // scls only by k_string_starts
+    hipLaunchKernelGGL(k_dsu_init, dim3(nblk(n_u)), dim3(256), 0, st, dsu.a, n_u, has_terminal);
+    hipLaunchKernelGGL(k_dsu_unite_mates, dim3(nblk(2 * n_u)), dim3(256), 0, st, dsu, p->mate, 2 * n_u);
+    hipLaunchKernelGGL(k_dsu_mark_terminals, dim3(nblk(n_u)), dim3(256), 0, st, dsu, p->mate, n_u, has_terminal);
+    hipLaunchKernelGGL(k_dsu_open_paths, dim3(nblk(n_u)), dim3(256), 0, st, dsu, has_terminal, n_u, p->visited);
+    hipLaunchKernelGGL(k_loop_cut, dim3(unsigned((n_u + 63) / 64)), dim3(64), 0, st, p->mate, n_u,
+                       directed, p->visited, p->sc_nodes, p->sc_parent, p->sc_rank, p->sc_used);
+  }
+  // the walks over the (now loop-free) path cover, by pointer jumping; the words reuse the
+  // matching's priorities, the string ids of the starts its candidates
+  unsigned long long* walk = p->best_prio;
+  uint32_t* sid_at = p->best_w;
+  hipLaunchKernelGGL(k_walk_init, dim3(nblk(2 * n_u)), dim3(256), 0, st, p->mate, p->u_len, 2 * n_u, walk);
+  // log5(2 n_u) + 3 launches end every walk of a loop-free cover; enqueued at once (a round after the last
+  // one that changed anything returns at its first load), the last flag is looked at with the sizes below
+  walk_rounds = 3;  // (four hops per launch: log5 of the states, and spare)
+  for (int64_t x = 2 * n_u; x > 1; x /= (kJumpHops + 1)) walk_rounds++;
+  walk_rounds = std::min(walk_rounds, kWalkRoundsMax);
+  for (int round = 0; round < walk_rounds; round++)
+    hipLaunchKernelGGL(k_walk_jump, dim3(nblk(2 * n_u)), dim3(256), 0, st, 2 * n_u, walk,
+                       round ? &ctl->walk_live[round - 1] : nullptr, &ctl->walk_live[round]);
+  hipLaunchKernelGGL(k_string_starts, dim3(nblk(n_u)), dim3(256), 0, st, p->mate, p->u_len, walk, n_u,
+                     directed, p->scls, p->s_nk, p->str_start);
+  hipLaunchKernelGGL(k_string_counts, dim3(nblk(n_u)), dim3(256), 0, st, p->scls, n_u, slow, p->sc01,
+                     p->sc2);
+  arena_reset(ctx);
+  int64_t* d_t2 = ctl->t2;
+  KSH_TRY(scan_exclusive_i64(ctx, p->sc01, p->sc01, n_u, d_t2));
+  KSH_TRY(scan_exclusive_i64(ctx, p->sc2, p->sc2, n_u, d_t2 + 1));
+  hipLaunchKernelGGL(k_string_ids, dim3(nblk(n_u)), dim3(256), 0, st, n_u, p->scls, p->sc01, p->sc2, p->s_nk, d_t2,
+                     slow, k, sid_at, p->lens, p->str_start);
+  hipLaunchKernelGGL(k_string_assign, dim3(nblk(n_u)), dim3(256), 0, st, p->u_len, walk, n_u, p->scls, sid_at,
+                     slow, p->u_sid, p->u_koff, p->u_flip, &ctl->walk_live[walk_rounds - 1]);
+  *walk_rounds_out = walk_rounds;
+  return KSH_OK;
 }
 
 template <typename KeyT>
@@ -4172,67 +4249,7 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
   } else {
     hipLaunchKernelGGL((k_edges<KeyT>), dim3(nblk(2 * n_u)), dim3(256), 0, st, set, 2 * n_u, directed,
                        p->u_first, p->u_last, p->head, p->uid, p->edges, p->mate);
-    p->rounds = 0;
-    const bool slow = mode == 2;
-    if (slow) {
-      hipLaunchKernelGGL(k_match_slow, dim3(1), dim3(64), 0, st, p->edges, p->mate, n_u);
-    } else {
-      // rounds in batches, one look at the flags per batch: four rounds first (every round past the last one that
-      // found something is two launches that return at once, some 9 us each), then eight at a time
-      for (bool more = true; more;) {
-        if (p->rounds) KSH_HIP(hipMemsetAsync(ctl->match_live, 0, sizeof(ctl->match_live), st));
-        const int batch = p->rounds ? kMatchBatch : kMatchFirst;
-        for (int r = 0; r < batch; r++) {
-          hipLaunchKernelGGL(k_match_best, dim3(nblk(2 * n_u)), dim3(256), 0, st, p->edges, p->mate, 2 * n_u, directed,
-                             p->best_prio, p->best_w, r ? &ctl->match_live[r - 1] : nullptr, &ctl->match_live[r]);
-          hipLaunchKernelGGL(k_match_commit, dim3(nblk(2 * n_u)), dim3(256), 0, st, p->best_prio, p->best_w, 2 * n_u,
-                             &ctl->match_live[r], p->mate);
-        }
-        KSH_HIP(hipMemcpyAsync(ctx->h_pinned, ctl->match_live, batch * sizeof(int), hipMemcpyDeviceToHost, st));
-        KSH_HIP(hipStreamSynchronize(st));
-        const int* live = reinterpret_cast<const int*>(ctx->h_pinned);
-        int ran = 0;
-        while (ran < batch && live[ran]) ran++;
-        more = ran == batch;
-        p->rounds += more ? batch : ran + 1;  // (the round that found nothing counts, as before)
-        if (p->rounds > 100000) return fail(KSH_INTERNAL, "matching did not converge");
-      }
-      // the path extension of fast = false never closes a loop; the greedy matching can:
-      // components of the chosen edges (parallel union-find), the ones without a terminal are loops
-      DevDsu dsu{reinterpret_cast<unsigned long long*>(p->sc01)};  // sc01 is only filled by k_string_counts
-      uint8_t* has_terminal = p->scls;                             // scls only by k_string_starts
-      hipLaunchKernelGGL(k_dsu_init, dim3(nblk(n_u)), dim3(256), 0, st, dsu.a, n_u, has_terminal);
-      hipLaunchKernelGGL(k_dsu_unite_mates, dim3(nblk(2 * n_u)), dim3(256), 0, st, dsu, p->mate, 2 * n_u);
-      hipLaunchKernelGGL(k_dsu_mark_terminals, dim3(nblk(n_u)), dim3(256), 0, st, dsu, p->mate, n_u, has_terminal);
-      hipLaunchKernelGGL(k_dsu_open_paths, dim3(nblk(n_u)), dim3(256), 0, st, dsu, has_terminal, n_u, p->visited);
-      hipLaunchKernelGGL(k_loop_cut, dim3(unsigned((n_u + 63) / 64)), dim3(64), 0, st, p->mate, n_u,
-                         directed, p->visited, p->sc_nodes, p->sc_parent, p->sc_rank, p->sc_used);
-    }
-    // the walks over the (now loop-free) path cover, by pointer jumping; the words reuse the
-    // matching's priorities, the string ids of the starts its candidates
-    unsigned long long* walk = p->best_prio;
-    uint32_t* sid_at = p->best_w;
-    hipLaunchKernelGGL(k_walk_init, dim3(nblk(2 * n_u)), dim3(256), 0, st, p->mate, p->u_len, 2 * n_u, walk);
-    // log5(2 n_u) + 3 launches end every walk of a loop-free cover; enqueued at once (a round after the last
-    // one that changed anything returns at its first load), the last flag is looked at with the sizes below
-    walk_rounds = 3;  // (four hops per launch: log5 of the states, and spare)
-    for (int64_t x = 2 * n_u; x > 1; x /= (kJumpHops + 1)) walk_rounds++;
-    walk_rounds = std::min(walk_rounds, kWalkRoundsMax);
-    for (int round = 0; round < walk_rounds; round++)
-      hipLaunchKernelGGL(k_walk_jump, dim3(nblk(2 * n_u)), dim3(256), 0, st, 2 * n_u, walk,
-                         round ? &ctl->walk_live[round - 1] : nullptr, &ctl->walk_live[round]);
-    hipLaunchKernelGGL(k_string_starts, dim3(nblk(n_u)), dim3(256), 0, st, p->mate, p->u_len, walk, n_u,
-                       directed, p->scls, p->s_nk, p->str_start);
-    hipLaunchKernelGGL(k_string_counts, dim3(nblk(n_u)), dim3(256), 0, st, p->scls, n_u, slow, p->sc01,
-                       p->sc2);
-    arena_reset(ctx);
-    int64_t* d_t2 = ctl->t2;
-    KSH_TRY(scan_exclusive_i64(ctx, p->sc01, p->sc01, n_u, d_t2));
-    KSH_TRY(scan_exclusive_i64(ctx, p->sc2, p->sc2, n_u, d_t2 + 1));
-    hipLaunchKernelGGL(k_string_ids, dim3(nblk(n_u)), dim3(256), 0, st, n_u, p->scls, p->sc01, p->sc2, p->s_nk, d_t2,
-                       slow, g->k, sid_at, p->lens, p->str_start);
-    hipLaunchKernelGGL(k_string_assign, dim3(nblk(n_u)), dim3(256), 0, st, p->u_len, walk, n_u, p->scls, sid_at,
-                       slow, p->u_sid, p->u_koff, p->u_flip, &ctl->walk_live[walk_rounds - 1]);
+    KSH_TRY(cover_stage(ctx, p, n_u, directed, mode == 2, g->k, &walk_rounds));
   }
   // string starts in bases (a scan over n_u slots: the slots past the last string hold zero)
   arena_reset(ctx);
@@ -4332,6 +4349,143 @@ int encode_write_t(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
   return KSH_OK;
 }
 
+// ---------------------------------------------------------------------------------- cover
+// ksh_spss_cover_plan: the caller's strings are the unitigs.  Their end k-mers give the edge table
+// (k_cover_ends / k_cover_edges, ksh_cover.hip), cover_stage does the rest of the path cover as it does for the
+// encode, and the plan holds everything the write needs: the strings' places and orientations, the output
+// layout.  The plan takes the encode's slot (ctx->enc_state): a plan of either kind replaces the other.
+// at most 2^30 - 1 strings: the walks' records hold 31-bit state ids (2 per string)
+constexpr int64_t kCoverMaxStrings = (int64_t(1) << 30) - 1;
+int cover_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* in, bool directed, bool slow,
+               int64_t* n_strings, int64_t* n_bases) {
+  free_plan(ctx);
+  EncPlan* p = new EncPlan;
+  ctx->enc_state = p;
+  p->cover = true;
+  p->g = *g;
+  p->in = *in;
+  p->directed = directed;
+  p->mode = slow ? 2 : 0;
+  const int64_t n = in->n_strings;
+  p->n = n;
+  p->n_u = n;
+  if (n == 0) {
+    p->cover_ready = true;
+    *n_strings = 0;
+    *n_bases = 0;
+    return KSH_OK;
+  }
+  const int k = g->k;
+  const int n_tables = directed ? 2 : 1;
+  uint64_t cap = 1;
+  while (cap < uint64_t(4 * n)) cap <<= 1;
+  const size_t block = al(sizeof(EncCtl)) + al(kCoverErrCount * 8 + 8) + 7 * al(size_t(n) * 4) +
+                       al(size_t(8 * n) * 4) + 2 * al(size_t(2 * n) * 4) + al(size_t(2 * n) * 8) + 3 * al(size_t(n)) +
+                       5 * al(size_t(n + 1) * 8) + 2 * al(size_t(n) * 8) + al(n_tables * cap * 8) +
+                       al(n_tables * cap * 4) + 4096;
+  KSH_TRY(arena_reserve(ctx, size_t(n / 256 + 4096) * 8 * 2 + (1u << 16)));
+  KSH_TRY(pool_alloc(ctx, block, reinterpret_cast<void**>(&p->ublock)));
+  char* at = p->ublock;
+  p->ctl = reinterpret_cast<EncCtl*>(carve<char>(at, sizeof(EncCtl)));
+  unsigned long long* err = carve<unsigned long long>(at, kCoverErrCount + 1);  // + the input's base total
+  int64_t* in_total = reinterpret_cast<int64_t*>(err + kCoverErrCount);
+  p->u_len = carve<uint32_t>(at, size_t(n));
+  p->u_sid = carve<uint32_t>(at, size_t(n));
+  p->u_koff = carve<uint32_t>(at, size_t(n));
+  p->lens = carve<uint32_t>(at, size_t(n));
+  p->sc_nodes = carve<uint32_t>(at, size_t(n));
+  p->sc_parent = carve<uint32_t>(at, size_t(n));
+  p->sc_rank = carve<uint32_t>(at, size_t(n));
+  p->edges = carve<uint32_t>(at, size_t(8 * n));
+  p->mate = carve<uint32_t>(at, size_t(2 * n));
+  p->best_w = carve<uint32_t>(at, size_t(2 * n));
+  p->best_prio = carve<unsigned long long>(at, size_t(2 * n));
+  p->visited = carve<uint8_t>(at, size_t(n));
+  p->scls = carve<uint8_t>(at, size_t(n));
+  p->u_flip = carve<uint8_t>(at, size_t(n));
+  p->s_nk = carve<int64_t>(at, size_t(n + 1));
+  p->sc01 = carve<int64_t>(at, size_t(n + 1));
+  p->sc2 = carve<int64_t>(at, size_t(n + 1));
+  p->str_start = carve<int64_t>(at, size_t(n + 1));
+  p->in_start = carve<int64_t>(at, size_t(n + 1));
+  uint64_t* first = carve<uint64_t>(at, size_t(n));
+  uint64_t* last = carve<uint64_t>(at, size_t(n));
+  unsigned long long* keys = carve<unsigned long long>(at, n_tables * cap);
+  uint32_t* vals = carve<uint32_t>(at, n_tables * cap);
+  KSH_BOUND(size_t(at - p->ublock) <= block);
+  p->sc_used = &p->ctl->sc_used;
+  EncCtl* ctl = p->ctl;
+  hipStream_t st = ctx->stream;
+
+  KSH_HIP(hipMemsetAsync(ctl, 0, sizeof(EncCtl), st));
+  KSH_HIP(hipMemsetAsync(err, 0xFF, kCoverErrCount * 8, st));
+  KSH_HIP(hipMemsetAsync(keys, 0xFF, n_tables * cap * 8, st));
+  // the input strings' base offsets; every precondition is checked before the path cover starts
+  arena_reset(ctx);
+  cover_launch_sizes(st, in->d_lens, n, k, p->in_start);
+  KSH_TRY(scan_exclusive_i64(ctx, p->in_start, p->in_start, n, in_total));
+  cover_launch_ends(st, in, p->in_start, in_total, k, directed, first, last, keys, vals, cap, err);
+  KSH_HIP(hipGetLastError());
+  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, err, (kCoverErrCount + 1) * 8, hipMemcpyDeviceToHost, st));
+  KSH_HIP(hipStreamSynchronize(st));
+  const unsigned long long* e = reinterpret_cast<const unsigned long long*>(ctx->h_pinned);
+  if (e[kCoverErrBases] != ~0ull)
+    return fail(KSH_INVALID_ARGUMENT, "cover: the strings' lengths (lens + K) add up to %lld bases, not n_bases = %lld",
+                (long long)ctx->h_pinned[kCoverErrCount], (long long)in->n_bases);
+  if (e[kCoverErrPalindrome] != ~0ull)
+    return fail(KSH_INVALID_ARGUMENT, "cover: an end k-mer of string %llu is its own reverse complement (even k): "
+                                      "not supported", e[kCoverErrPalindrome]);
+  if (e[kCoverErrSameEnds] != ~0ull)
+    return fail(KSH_INVALID_ARGUMENT, "cover: string %llu is longer than K and its first and last k-mers have the "
+                                      "same canonical form", e[kCoverErrSameEnds]);
+  if (e[kCoverErrDupEnd] != ~0ull)
+    return fail(KSH_INVALID_ARGUMENT, "cover: an end k-mer of string %llu is, up to reverse complement, an end "
+                                      "k-mer of another string too (a string given twice, or with its reverse "
+                                      "complement)", e[kCoverErrDupEnd]);
+  if (e[kCoverErrDupFirst] != ~0ull)
+    return fail(KSH_INVALID_ARGUMENT, "cover: the first k-mer of string %llu is the first k-mer of another string "
+                                      "too (repeated first k-mer)", e[kCoverErrDupFirst]);
+  if (e[kCoverErrDupLast] != ~0ull)
+    return fail(KSH_INVALID_ARGUMENT, "cover: the last k-mer of string %llu is the last k-mer of another string "
+                                      "too (repeated last k-mer)", e[kCoverErrDupLast]);
+
+  cover_launch_edges(st, first, last, in->d_lens, n, k, directed, keys, vals, cap, p->u_len, p->edges, p->mate);
+  int walk_rounds = 0;
+  KSH_TRY(cover_stage(ctx, p, n, directed, slow, k, &walk_rounds));
+  arena_reset(ctx);
+  KSH_TRY(scan_exclusive_i64(ctx, p->str_start, p->str_start, n, &ctl->n_bases));
+  KSH_HIP(hipGetLastError());
+  constexpr size_t kTail = sizeof(EncCtl) - offsetof(EncCtl, t2);
+  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, ctl->t2, kTail, hipMemcpyDeviceToHost, st));
+  KSH_HIP(hipStreamSynchronize(st));
+  const int* walk_live_host = reinterpret_cast<const int*>(reinterpret_cast<const char*>(ctx->h_pinned) +
+                                                           (offsetof(EncCtl, walk_live) - offsetof(EncCtl, t2)));
+  if (walk_live_host[walk_rounds - 1]) return fail(KSH_INTERNAL, "the path cover still holds a loop");
+  p->n_strings = (ctx->h_pinned[0] & 0xFFFFFFFF) + (ctx->h_pinned[0] >> 32) + ctx->h_pinned[1];
+  p->n_bases = ctx->h_pinned[2];
+  p->cover_ready = true;
+  *n_strings = p->n_strings;
+  *n_bases = p->n_bases;
+  return KSH_OK;
+}
+
+int cover_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+  EncPlan* p = static_cast<EncPlan*>(ctx->enc_state);
+  if (p->n == 0) return KSH_OK;
+  hipStream_t st = ctx->stream;
+  void* tmp = nullptr;
+  KSH_TRY(pool_alloc(ctx, size_t(p->n_bases) + 64, &tmp));
+  uint8_t* bytes = static_cast<uint8_t*>(tmp);
+  cover_launch_emit(st, &p->in, p->in_start, p->u_len, p->u_sid, p->u_koff, p->u_flip, p->str_start, p->g.k,
+                    p->n_bases, bytes);
+  const int64_t n_words = (p->n_bases + 31) / 32;
+  hipLaunchKernelGGL(k_pack, dim3(nblk(n_words)), dim3(256), 0, st, bytes, p->n_bases, n_words, d_words);
+  KSH_HIP(hipMemcpyAsync(d_lens, p->lens, size_t(p->n_strings) * 4, hipMemcpyDeviceToDevice, st));
+  KSH_HIP(hipGetLastError());
+  pool_free(ctx, tmp);
+  return KSH_OK;
+}
+
 }  // namespace ksh
 
 using namespace ksh;
@@ -4356,6 +4510,7 @@ int ksh_spss_encode_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
   if (!ctx) return fail(KSH_INVALID_ARGUMENT, "ctx is NULL");
   EncPlan* p = static_cast<EncPlan*>(ctx->enc_state);
   if (!p) return fail(KSH_FAILED_PRECONDITION, "ksh_spss_encode_write without ksh_spss_encode_plan");
+  if (p->cover) return fail(KSH_FAILED_PRECONDITION, "ksh_spss_encode_write: the current plan is a cover plan");
   if (p->n > 0 && (!d_words || !d_lens)) return fail(KSH_INVALID_ARGUMENT, "NULL output");
   KSH_HIP(hipSetDevice(ctx->device));
   return KSH_BY_KEY(p->g.key_bytes, encode_write_t, ctx, d_words, d_lens);
@@ -4365,6 +4520,7 @@ int ksh_spss_encode_routes(ksh_ctx* ctx, int64_t* routes) {
   if (!ctx || !routes) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
   EncPlan* p = static_cast<EncPlan*>(ctx->enc_state);
   if (!p) return fail(KSH_FAILED_PRECONDITION, "no encode plan");
+  if (p->cover) return fail(KSH_FAILED_PRECONDITION, "ksh_spss_encode_routes: the current plan is a cover plan");
   *routes = p->routes;
   return KSH_OK;
 }
@@ -4389,6 +4545,47 @@ int ksh_debug_set_probe_trace(void* d_buf, long long rows) {
 #endif
 
 int ksh_spss_encode_release(ksh_ctx* ctx) {
+  if (ctx) free_plan(ctx);
+  return KSH_OK;
+}
+
+int ksh_spss_cover_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* unitigs, int canonical, int fast,
+                        int64_t* n_strings, int64_t* n_bases) {
+  if (!ctx || !unitigs || !n_strings || !n_bases) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
+  KSH_TRY(check_geom(g));
+  const int64_t n = unitigs->n_strings;
+  if (n < 0 || unitigs->n_bases < 0 || (n > 0 && (!unitigs->d_words || !unitigs->d_lens)))
+    return fail(KSH_INVALID_ARGUMENT, "bad unitig view");
+  if (n > kCoverMaxStrings)
+    return fail(KSH_INVALID_ARGUMENT, "cover: %lld strings, at most %lld", (long long)n, (long long)kCoverMaxStrings);
+  if (unitigs->n_bases - n * (g->k - 1) >= int64_t(0x7FFFFFF0))
+    return fail(KSH_INVALID_ARGUMENT, "cover: too many k-mers for 32-bit path weights");
+  KSH_HIP(hipSetDevice(ctx->device));
+  return cover_plan(ctx, g, unitigs, !canonical, canonical && !fast, n_strings, n_bases);
+}
+
+int ksh_spss_cover_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+  if (!ctx) return fail(KSH_INVALID_ARGUMENT, "ctx is NULL");
+  EncPlan* p = static_cast<EncPlan*>(ctx->enc_state);
+  if (!p || !p->cover) return fail(KSH_FAILED_PRECONDITION, "ksh_spss_cover_write without ksh_spss_cover_plan");
+  if (!p->cover_ready) return fail(KSH_FAILED_PRECONDITION, "ksh_spss_cover_write after a failed ksh_spss_cover_plan");
+  if (p->n > 0 && (!d_words || !d_lens)) return fail(KSH_INVALID_ARGUMENT, "NULL output");
+  KSH_HIP(hipSetDevice(ctx->device));
+  return cover_write(ctx, d_words, d_lens);
+}
+
+int ksh_spss_cover_stats(ksh_ctx* ctx, int64_t stats[4]) {
+  if (!ctx || !stats) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
+  EncPlan* p = static_cast<EncPlan*>(ctx->enc_state);
+  if (!p || !p->cover) return fail(KSH_FAILED_PRECONDITION, "no cover plan");
+  stats[0] = p->n_u;
+  stats[1] = p->rounds;
+  stats[2] = p->n_strings;
+  stats[3] = p->n_bases;
+  return KSH_OK;
+}
+
+int ksh_spss_cover_release(ksh_ctx* ctx) {
   if (ctx) free_plan(ctx);
   return KSH_OK;
 }

@@ -174,6 +174,21 @@ int check_view(const ksh_set_view* v, const char* name);  // ksh_pair.hip
 inline int64_t n_buckets(const ksh_geom* g) { return int64_t(1) << g->n_bucket_bits; }
 inline int key_bits(const ksh_geom* g) { return 2 * g->k - g->n_bucket_bits; }
 
+// Kernels of ksh_spss_cover_* (ksh_cover.hip); the plan lives beside the encode's (ksh_encode.hip), whose
+// unitig-level stage it shares.  err[kCoverErr*] receives the smallest string index that violates a precondition.
+enum { kCoverErrBases = 0, kCoverErrPalindrome, kCoverErrSameEnds, kCoverErrDupEnd, kCoverErrDupFirst,
+       kCoverErrDupLast, kCoverErrCount };
+void cover_launch_sizes(hipStream_t st, const uint32_t* lens, int64_t n, int k, int64_t* sizes);
+void cover_launch_ends(hipStream_t st, const ksh_spss_view* in, const int64_t* in_start, const int64_t* total,
+                       int k, bool directed, uint64_t* first, uint64_t* last, unsigned long long* keys,
+                       uint32_t* vals, uint64_t cap, unsigned long long* err);
+void cover_launch_edges(hipStream_t st, const uint64_t* first, const uint64_t* last, const uint32_t* lens, int64_t n,
+                        int k, bool directed, const unsigned long long* keys, const uint32_t* vals, uint64_t cap,
+                        uint32_t* u_len, uint32_t* edges, uint32_t* mate);
+void cover_launch_emit(hipStream_t st, const ksh_spss_view* in, const int64_t* in_start, const uint32_t* u_len,
+                       const uint32_t* u_sid, const uint32_t* u_koff, const uint8_t* u_flip, const int64_t* str_start,
+                       int k, int64_t n_bases, uint8_t* bytes);
+
 hipEvent_t timer_event(ksh_ctx* ctx, size_t* index);
 void free_plan(ksh_ctx* ctx);  // ksh_encode.hip
 

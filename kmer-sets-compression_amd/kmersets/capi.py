@@ -138,6 +138,11 @@ def lib():
         "ksh_spss_encode_stats": (C.c_int, [vp, C.POINTER(i64)]),
         "ksh_spss_encode_routes": (C.c_int, [vp, C.POINTER(i64)]),
         "ksh_spss_encode_release": (C.c_int, [vp]),
+        "ksh_spss_cover_plan": (C.c_int, [vp, GP, C.POINTER(SpssView), C.c_int, C.c_int, C.POINTER(i64),
+                                          C.POINTER(i64)]),
+        "ksh_spss_cover_write": (C.c_int, [vp, vp, vp]),
+        "ksh_spss_cover_stats": (C.c_int, [vp, C.POINTER(i64)]),
+        "ksh_spss_cover_release": (C.c_int, [vp]),
         "ksh_set_union_plan": (C.c_int, [vp, GP, SP, SP, vp, C.POINTER(i64)]),
         "ksh_set_union_write": (C.c_int, [vp, GP, SP, SP, vp]),
         "ksh_svb_encode_0124": (C.c_int, [vp, vp, i64, vp, C.POINTER(i64)]),
@@ -574,6 +579,27 @@ class Context:
     def spss_encode_stats(self):
         st = (C.c_int64 * 4)()
         check(lib().ksh_spss_encode_stats(self.h, st))
+        return {"unitigs": st[0], "rounds": st[1], "strings": st[2], "bases": st[3]}
+
+    # GetSPSSCanonical / GetSPSS from caller-supplied unitigs -----------------------------------
+    def spss_cover(self, unitigs, canonical=True, fast=True):
+        """The path cover of a DeviceSpss whose strings are unitigs (GetSPSSCanonical(unitigs, prefixes, suffixes,
+        fast), or GetSPSS(unitigs, prefixes) when canonical is False).  Returns a DeviceSpss; the input must
+        meet the preconditions of ksh_spss_cover_plan (include/kmersets_hip.h), else KshError."""
+        import torch
+
+        ns, nbases = C.c_int64(), C.c_int64()
+        v = unitigs.view()
+        check(lib().ksh_spss_cover_plan(self.h, C.byref(unitigs.g), C.byref(v), int(canonical), int(fast),
+                                        C.byref(ns), C.byref(nbases)))
+        words = torch.empty(max((nbases.value + 31) // 32, 1), dtype=torch.int64, device=self.device)
+        lens = torch.empty(max(ns.value, 1), dtype=torch.int32, device=self.device)
+        check(lib().ksh_spss_cover_write(self.h, words.data_ptr(), lens.data_ptr()))
+        return DeviceSpss(unitigs.g, words, lens, ns.value, nbases.value)
+
+    def spss_cover_stats(self):
+        st = (C.c_int64 * 4)()
+        check(lib().ksh_spss_cover_stats(self.h, st))
         return {"unitigs": st[0], "rounds": st[1], "strings": st[2], "bases": st[3]}
 
     ROUTES = ("probe_staged", "rc_1024", "rc_512", "rc_256", "rc_64", "rc_batched", "scatter_two_level",
