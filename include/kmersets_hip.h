@@ -229,10 +229,14 @@ int ksh_spss_size(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int64
  *        (an upper bound on the set size: repeated k-mers collapse in write).
  * write: scatter + per-bucket sort, duplicates dropped; d_keys holds n_keys(plan)
  *        keys; d_offsets is rewritten if duplicates were dropped; n_keys = set size.
- * Limit: n_bucket_bits <= 14 (KSH_INVALID_ARGUMENT beyond): the counting pass keeps one 4-byte counter per
- * bucket in a workgroup's 64 KB of LDS.  The reference's template takes any N (lib/core/kmer_set.h:20-31); its
- * CLIs instantiate N = 10 and 14 (src/kmerset-multiple-compress.cc:156-157).  The same limit holds for
- * ksh_kmer_count_write and for everything that decodes (ksh_kss_build*, ksh_kss_get, ksh_spss_from_text_*). */
+ * Any n_bucket_bits the geometry allows (<= 24, as ksh_set_view).  The counting pass keeps one 4-byte counter per
+ * bucket in a workgroup's 64 KB of LDS, so above N = 14 the decode takes a wide route: it counts, scatters and
+ * sorts on 2^14 coarse buckets with a composite key (the N - 14 low bucket bits, then the key; a wider scratch
+ * type when 2K - 14 bits exceed the key type), then one pass derives the fine offsets and one narrows the keys.
+ * There, after plan, d_offsets holds the coarse layout only (every coarse bucket's range on its last fine bucket;
+ * d_offsets[2^N] = n_keys): the fine offsets are what write leaves.  The wide route costs about one extra read
+ * and write of the keys.  The same holds for ksh_kmer_count_write and for everything that decodes
+ * (ksh_kss_build*, ksh_kss_get, ksh_spss_from_text_*). */
 int ksh_spss_decode_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int canonical,
                          int64_t* d_offsets, int64_t* n_keys);
 int ksh_spss_decode_write(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int canonical,

@@ -728,6 +728,7 @@ struct DecodeState {
   unsigned long long* end_bits;
   int64_t* str_start;   // [n_strings + 1]
   int64_t* totals;      // [n_buckets + 1]
+  int64_t* coarse;      // wide route only: [2^kCoarseBits + 1] coarse bucket offsets, plan -> write
 };
 
 inline size_t a256(size_t x) { return (x + 255) & ~size_t(255); }
@@ -750,6 +751,7 @@ void decode_geometry(const ksh_spss_view* s, int64_t* n_words, int64_t* n_end_wo
   *words_per_group = (*n_words + g - 1) / g;
 }
 
+// nb: the buckets the counting pass works on (2^kCoarseBits on the wide route)
 void decode_carve(ksh_ctx* ctx, int64_t groups, int64_t nb, int64_t n_end_words, int64_t n_strings,
                   DecodeState* st) {
   char* at = ctx->slot[kSlotDecode];
@@ -760,6 +762,66 @@ void decode_carve(ksh_ctx* ctx, int64_t groups, int64_t nb, int64_t n_end_words,
   st->str_start = reinterpret_cast<int64_t*>(at);
   at += a256(size_t(n_strings + 1) * 8);
   st->totals = reinterpret_cast<int64_t*>(at);
+  at += a256(size_t(nb + 2) * 8);
+  st->coarse = reinterpret_cast<int64_t*>(at);
+}
+
+// ---- the wide route: N > 14 ------------------------------------------------------------------
+// The counting pass keeps one LDS counter per bucket, so 2^14 is as far as it goes.  Above that the whole
+// pipeline runs on a coarse geometry: 2^14 buckets and a COMPOSITE key of 2K - 14 bits, the N - 14 low
+// bucket bits followed by the key.  Coarse bucket c is exactly fine buckets [c << s, (c + 1) << s) (s = N - 14),
+// so the sorted, de-duplicated composites of a coarse bucket are ordered by fine bucket, then by key.  Two
+// passes finish the job: k_fine_offsets (one thread per fine bucket, a lower bound inside its coarse bucket)
+// and k_narrow_buckets (composite -> key, closing the gaps that dropped duplicates left).  The composite
+// needs a wider type than the key when 2K - 14 exceeds it (2-byte keys with K >= 16, 4-byte keys with
+// K >= 24): those geometries sort in a scratch buffer of the wider type and narrow into the keys.
+constexpr int kCoarseBits = 14;
+static_assert((1 << kCoarseBits) == kMaxLdsBuckets, "one LDS counter per coarse bucket");
+inline bool wide_route(const ksh_geom* g) { return g->n_bucket_bits > kCoarseBits; }
+
+__global__ __launch_bounds__(256) void k_broadcast_coarse(const int64_t* __restrict__ coarse, int sub_bits,
+                                                           int64_t n_fine, int64_t* __restrict__ fine) {
+  const int64_t f = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (f <= n_fine) fine[f] = coarse[f >> sub_bits];
+}
+
+// fine[f] = where fine bucket f starts: coarse bucket c = f >> sub_bits holds its sorted unique composites
+// at comp[old_off[c], old_off[c] + new_off[c + 1] - new_off[c]) and goes to new_off[c]
+template <typename CT>
+__global__ __launch_bounds__(256) void k_fine_offsets(const int64_t* __restrict__ old_off,
+                                                       const int64_t* __restrict__ new_off,
+                                                       const CT* __restrict__ comp, int sub_bits, int key_bits,
+                                                       int64_t n_fine, int64_t* __restrict__ fine) {
+  const int64_t f = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (f > n_fine) return;
+  const int64_t c = f >> sub_bits;
+  const uint64_t j = uint64_t(f) & ((uint64_t(1) << sub_bits) - 1);
+  if (j == 0) {  // (also f == n_fine: c is then the end of the coarse offsets)
+    fine[f] = new_off[c];
+    return;
+  }
+  const CT* p = comp + old_off[c];
+  const CT target = CT(j << key_bits);
+  int64_t lo = 0, hi = new_off[c + 1] - new_off[c];
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (p[mid] < target) lo = mid + 1;
+    else hi = mid;
+  }
+  fine[f] = new_off[c] + lo;
+}
+
+// One workgroup per coarse bucket: its unique composites (at old_off) -> keys (at new_off).  In place when
+// src and dst are one buffer and nothing was dropped (old_off == new_off: a thread reads what it writes).
+template <typename CT, typename KeyT>
+__global__ __launch_bounds__(256) void k_narrow_buckets(const int64_t* __restrict__ old_off,
+                                                         const int64_t* __restrict__ new_off, const CT* src,
+                                                         KeyT* dst, uint64_t key_mask) {
+  const int64_t b = blockIdx.x;
+  const int64_t cnt = new_off[b + 1] - new_off[b];
+  const CT* s = src + old_off[b];
+  KeyT* d = dst + new_off[b];
+  for (int64_t i = threadIdx.x; i < cnt; i += 256) d[i] = KeyT(uint64_t(s[i]) & key_mask);
 }
 
 template <typename KeyT>
@@ -773,15 +835,21 @@ int decode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int c
     ctx->dec_src = s->d_words;
     return KSH_OK;
   }
+  // the buckets and key bits the counting works on: the coarse geometry on the wide route
+  const bool wide = wide_route(g);
+  const int64_t nbw = wide ? (int64_t(1) << kCoarseBits) : nb;
+  const int kbw = wide ? 2 * g->k - kCoarseBits : key_bits(g);
   int64_t n_words, n_end_words, groups, wpg;
   decode_geometry(s, &n_words, &n_end_words, &groups, &wpg);
-  const size_t bytes = a256(size_t(groups) * nb * 4) + a256(size_t(n_end_words) * 8) +
-                       a256(size_t(s->n_strings + 1) * 8) + a256(size_t(nb + 2) * 8);
+  const size_t bytes = a256(size_t(groups) * nbw * 4) + a256(size_t(n_end_words) * 8) +
+                       a256(size_t(s->n_strings + 1) * 8) + a256(size_t(nbw + 2) * 8) +
+                       (wide ? a256(size_t(nbw + 1) * 8) : 0);
   KSH_TRY(slot_reserve(ctx, kSlotDecode, bytes));
   KSH_TRY(arena_reserve(ctx, size_t(s->n_strings / 256 + 4096) * 8 + (1u << 16)));
   arena_reset(ctx);
   DecodeState st;
-  decode_carve(ctx, groups, nb, n_end_words, s->n_strings, &st);
+  decode_carve(ctx, groups, nbw, n_end_words, s->n_strings, &st);
+  int64_t* offw = wide ? st.coarse : d_offsets;
 
   const unsigned sb = unsigned((s->n_strings + 255) / 256);
   hipLaunchKernelGGL(k_str_bases, dim3(sb), dim3(256), 0, ctx->stream, s->d_lens, s->n_strings, g->k,
@@ -792,17 +860,20 @@ int decode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int c
   hipLaunchKernelGGL(k_mark_ends, dim3(sb), dim3(256), 0, ctx->stream, st.str_start, s->n_strings,
                      st.end_bits);
   hipLaunchKernelGGL((k_decode<KeyT, false>), dim3(unsigned(groups)), dim3(kDecThreads),
-                     size_t(nb) * 4, ctx->stream, s->d_words, n_words, s->n_bases, st.end_bits,
-                     n_end_words, g->k, key_bits(g), int(nb), canonical_flag, wpg, st.hist, nullptr,
+                     size_t(nbw) * 4, ctx->stream, s->d_words, n_words, s->n_bases, st.end_bits,
+                     n_end_words, g->k, kbw, int(nbw), canonical_flag, wpg, st.hist, nullptr,
                      static_cast<KeyT*>(nullptr));
-  unsigned long long* d_max = reinterpret_cast<unsigned long long*>(st.totals + nb + 1);
+  unsigned long long* d_max = reinterpret_cast<unsigned long long*>(st.totals + nbw + 1);
   KSH_HIP(hipMemsetAsync(d_max, 0, 8, ctx->stream));
-  hipLaunchKernelGGL(k_hist_columns, dim3(unsigned((nb + 63) / 64)), dim3(64 * kColTeams), 0, ctx->stream,
-                     st.hist, groups, int(nb), st.totals, d_max);
-  KSH_TRY(scan_exclusive_i64(ctx, st.totals, d_offsets, nb, d_offsets + nb));
+  hipLaunchKernelGGL(k_hist_columns, dim3(unsigned((nbw + 63) / 64)), dim3(64 * kColTeams), 0, ctx->stream,
+                     st.hist, groups, int(nbw), st.totals, d_max);
+  KSH_TRY(scan_exclusive_i64(ctx, st.totals, offw, nbw, offw + nbw));
+  if (wide)  // (a valid layout until the write puts in the fine offsets: a coarse bucket's range on its last fine bucket)
+    hipLaunchKernelGGL(k_broadcast_coarse, dim3(unsigned(nb / 256 + 1)), dim3(256), 0, ctx->stream, st.coarse,
+                       g->n_bucket_bits - kCoarseBits, nb, d_offsets);
   KSH_HIP(hipGetLastError());
   // consistency: the strings must tile the base stream exactly
-  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, d_offsets + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
+  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, offw + nbw, 8, hipMemcpyDeviceToHost, ctx->stream));
   KSH_HIP(hipMemcpyAsync(ctx->h_pinned + 1, st.str_start + s->n_strings, 8, hipMemcpyDeviceToHost,
                          ctx->stream));
   KSH_HIP(hipMemcpyAsync(ctx->h_pinned + 2, d_max, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -819,22 +890,16 @@ int decode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int c
   return KSH_OK;
 }
 
+// Scatter of every k-mer into its bucket of `keys` (laid out by `offsets`, nbw = 2^nbits_w buckets of kbw key
+// bits), then the per-bucket sort: uniq counts in st.totals, *below (if any) per bucket; new_off / below are
+// carved from the arena.
 template <typename KeyT>
-int decode_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int canonical_flag,
-                   int64_t* d_offsets, void* d_keys, int64_t* n_keys, int cutoff, int64_t* n_below) {
-  const int64_t nb = n_buckets(g);
-  if (ctx->dec_src != s->d_words)
-    return fail(KSH_FAILED_PRECONDITION, "ksh_spss_decode_write without a matching decode_plan");
-  if (n_below) *n_below = 0;
-  if (ctx->dec_kmers == 0) {
-    *n_keys = 0;
-    return KSH_OK;
-  }
+int scatter_sort(ksh_ctx* ctx, const ksh_spss_view* s, const DecodeState& st, int k, int nbits_w, int kbw,
+                 int canonical_flag, const int64_t* offsets, KeyT* keys, int cutoff, bool want_below,
+                 int64_t** new_off, int64_t** below) {
+  const int64_t nb = int64_t(1) << nbits_w;
   int64_t n_words, n_end_words, groups, wpg;
   decode_geometry(s, &n_words, &n_end_words, &groups, &wpg);
-  DecodeState st;
-  decode_carve(ctx, groups, nb, n_end_words, s->n_strings, &st);
-  KeyT* keys = static_cast<KeyT*>(d_keys);
   // KSH_DECODE_SCATTER=direct: one scattered store per k-mer (k_decode<true>), for A/B runs and small inputs
   static const bool direct = [] {
     const char* e = getenv("KSH_DECODE_SCATTER");
@@ -844,7 +909,7 @@ int decode_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int 
     const char* e = getenv("KSH_DECODE_L2_MIN");  // (tests set it low)
     return e ? std::max<int64_t>(1024, atoll(e)) : int64_t(1) << 20;
   }();
-  if (!direct && ctx->dec_kmers >= two_level_min && g->n_bucket_bits > kDecSgBits && g->n_bucket_bits <= 15 &&
+  if (!direct && ctx->dec_kmers >= two_level_min && nbits_w > kDecSgBits && nbits_w <= 15 &&
       ctx->dec_kmers < int64_t(0xFFFFFFF0)) {
     void* tmp = nullptr;
     const size_t tk = (size_t(ctx->dec_kmers) * sizeof(KeyT) + 255) & ~size_t(255);
@@ -854,16 +919,16 @@ int decode_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int 
     uint32_t* cursor = reinterpret_cast<uint32_t*>(static_cast<char*>(tmp) + tk + ((size_t(ctx->dec_kmers) * 2 + 255) & ~size_t(255)));
     KSH_HIP(hipMemsetAsync(cursor, 0, size_t(nb) * 4, ctx->stream));
     hipLaunchKernelGGL((k_decode_l1<KeyT>), dim3(unsigned(groups)), dim3(kDecL1Threads), 0, ctx->stream, s->d_words,
-                       n_words, s->n_bases, st.end_bits, n_end_words, g->k, key_bits(g), g->n_bucket_bits,
-                       canonical_flag, wpg, st.hist, d_offsets, tmp_keys, tmp_b);
+                       n_words, s->n_bases, st.end_bits, n_end_words, k, kbw, nbits_w,
+                       canonical_flag, wpg, st.hist, offsets, tmp_keys, tmp_b);
     hipLaunchKernelGGL((k_decode_l2<KeyT>), dim3(unsigned((ctx->dec_kmers + kDecL2Tile - 1) / kDecL2Tile)),
-                       dim3(kDecL2Threads), 0, ctx->stream, ctx->dec_kmers, g->n_bucket_bits, d_offsets, tmp_keys, tmp_b,
+                       dim3(kDecL2Threads), 0, ctx->stream, ctx->dec_kmers, nbits_w, offsets, tmp_keys, tmp_b,
                        cursor, keys);
     pool_free(ctx, tmp);  // (single stream: the block is reused only behind these launches)
   } else {
     hipLaunchKernelGGL((k_decode<KeyT, true>), dim3(unsigned(groups)), dim3(kDecThreads),
                        size_t(nb) * 4, ctx->stream, s->d_words, n_words, s->n_bases, st.end_bits,
-                       n_end_words, g->k, key_bits(g), int(nb), canonical_flag, wpg, st.hist, d_offsets,
+                       n_end_words, k, kbw, int(nb), canonical_flag, wpg, st.hist, offsets,
                        keys);
   }
   // per-bucket sort + duplicate removal; uniq counts reuse st.totals.  Buckets larger than the
@@ -881,9 +946,9 @@ int decode_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int 
   }
   arena_reset(ctx);
   KSH_TRY(arena_reserve(ctx, 2 * a256(size_t(nb + 1) * 8) + (1u << 16)));
-  int64_t* new_off = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb + 1) * 8));
-  int64_t* below = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb + 1) * 8));
-  if (!new_off || !below) return fail(KSH_INTERNAL, "scratch arena too small");
+  *new_off = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb + 1) * 8));
+  *below = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb + 1) * 8));
+  if (!*new_off || !*below) return fail(KSH_INTERNAL, "scratch arena too small");
   {
     // (more than the 64 KB a kernel gets without asking)
     const uint32_t bit = 8u << (sizeof(KeyT) == 2 ? 0 : sizeof(KeyT) == 4 ? 1 : 2);
@@ -894,9 +959,96 @@ int decode_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int 
     }
   }
   hipLaunchKernelGGL((k_bucket_sort<KeyT>), dim3(unsigned(nb)), dim3(kSortThreads), kSortLdsBytes, ctx->stream,
-                     d_offsets, keys, scratch, st.totals, key_bits(g), cutoff, n_below ? below : nullptr);
+                     offsets, keys, scratch, st.totals, kbw, cutoff, want_below ? *below : nullptr);
   if (scratch) pool_free(ctx, scratch);
   KSH_HIP(hipGetLastError());
+  return KSH_OK;
+}
+
+// The wide route's write, sorting composites of type CT (KeyT or wider; in d_keys itself when as wide)
+template <typename KeyT, typename CT>
+int decode_write_wide(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int canonical_flag,
+                      int64_t* d_offsets, void* d_keys, int64_t* n_keys, int cutoff, int64_t* n_below) {
+  const int64_t nb = n_buckets(g), nbc = int64_t(1) << kCoarseBits;
+  const int sub_bits = g->n_bucket_bits - kCoarseBits, cbits = 2 * g->k - kCoarseBits;
+  int64_t n_words, n_end_words, groups, wpg;
+  decode_geometry(s, &n_words, &n_end_words, &groups, &wpg);
+  DecodeState st;
+  decode_carve(ctx, groups, nbc, n_end_words, s->n_strings, &st);
+  KeyT* keys = static_cast<KeyT*>(d_keys);
+  constexpr bool in_place = sizeof(CT) == sizeof(KeyT);
+  CT* comp = reinterpret_cast<CT*>(d_keys);
+  if (!in_place) {
+    void* ptr = nullptr;
+    KSH_TRY(pool_alloc(ctx, size_t(ctx->dec_kmers) * sizeof(CT), &ptr));
+    comp = static_cast<CT*>(ptr);
+  }
+  int64_t *new_off = nullptr, *below = nullptr;
+  KSH_TRY(scatter_sort<CT>(ctx, s, st, g->k, kCoarseBits, cbits, canonical_flag, st.coarse, comp, cutoff,
+                           n_below != nullptr, &new_off, &below));
+  KSH_TRY(scan_exclusive_i64(ctx, st.totals, new_off, nbc, new_off + nbc));
+  if (n_below) KSH_TRY(scan_exclusive_i64(ctx, below, below, nbc, below + nbc));
+  hipLaunchKernelGGL((k_fine_offsets<CT>), dim3(unsigned(nb / 256 + 1)), dim3(256), 0, ctx->stream, st.coarse,
+                     new_off, comp, sub_bits, key_bits(g), nb, d_offsets);
+  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, new_off + nbc, 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (n_below)
+    KSH_HIP(hipMemcpyAsync(ctx->h_pinned + 1, below + nbc, 8, hipMemcpyDeviceToHost, ctx->stream));
+  KSH_HIP(hipStreamSynchronize(ctx->stream));
+  const int64_t kept = ctx->h_pinned[0];
+  if (n_below) *n_below = ctx->h_pinned[1];
+  const uint64_t key_mask = key_bits(g) >= 64 ? ~uint64_t(0) : (uint64_t(1) << key_bits(g)) - 1;
+  void* tmp = nullptr;
+  const CT* src = comp;
+  if (in_place && kept != ctx->dec_kmers) {
+    // repeated k-mers in the input: the ranges move down, so read them from a copy (rare)
+    KSH_TRY(device_alloc(ctx, size_t(ctx->dec_kmers) * sizeof(CT), &tmp));
+    KSH_HIP(hipMemcpyAsync(tmp, comp, size_t(ctx->dec_kmers) * sizeof(CT), hipMemcpyDeviceToDevice, ctx->stream));
+    src = static_cast<const CT*>(tmp);
+  }
+  hipLaunchKernelGGL((k_narrow_buckets<CT, KeyT>), dim3(unsigned(nbc)), dim3(256), 0, ctx->stream, st.coarse,
+                     new_off, src, keys, key_mask);
+  KSH_HIP(hipGetLastError());
+  if (!in_place) pool_free(ctx, comp);
+  if (tmp) {
+    KSH_HIP(hipStreamSynchronize(ctx->stream));
+    KSH_HIP(hipFree(tmp));
+  }
+  *n_keys = kept;
+  return KSH_OK;
+}
+
+template <typename KeyT>
+int decode_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int canonical_flag,
+                   int64_t* d_offsets, void* d_keys, int64_t* n_keys, int cutoff, int64_t* n_below) {
+  const int64_t nb = n_buckets(g);
+  if (ctx->dec_src != s->d_words)
+    return fail(KSH_FAILED_PRECONDITION, "ksh_spss_decode_write without a matching decode_plan");
+  if (n_below) *n_below = 0;
+  if (ctx->dec_kmers == 0) {
+    *n_keys = 0;
+    return KSH_OK;
+  }
+  if (wide_route(g)) {
+    // the composite type: as wide as the 2K - 14 composite bits need, and no narrower than the key
+    const int cbits = 2 * g->k - kCoarseBits;
+    const size_t need = cbits <= 16 ? 2 : cbits <= 32 ? 4 : 8;
+    const size_t cb = std::max(need, sizeof(KeyT));
+    if constexpr (sizeof(KeyT) <= 2)
+      if (cb == 2)
+        return decode_write_wide<KeyT, uint16_t>(ctx, g, s, canonical_flag, d_offsets, d_keys, n_keys, cutoff, n_below);
+    if constexpr (sizeof(KeyT) <= 4)
+      if (cb == 4)
+        return decode_write_wide<KeyT, uint32_t>(ctx, g, s, canonical_flag, d_offsets, d_keys, n_keys, cutoff, n_below);
+    return decode_write_wide<KeyT, uint64_t>(ctx, g, s, canonical_flag, d_offsets, d_keys, n_keys, cutoff, n_below);
+  }
+  int64_t n_words, n_end_words, groups, wpg;
+  decode_geometry(s, &n_words, &n_end_words, &groups, &wpg);
+  DecodeState st;
+  decode_carve(ctx, groups, nb, n_end_words, s->n_strings, &st);
+  KeyT* keys = static_cast<KeyT*>(d_keys);
+  int64_t *new_off = nullptr, *below = nullptr;
+  KSH_TRY(scatter_sort<KeyT>(ctx, s, st, g->k, g->n_bucket_bits, key_bits(g), canonical_flag, d_offsets, keys,
+                             cutoff, n_below != nullptr, &new_off, &below));
   KSH_TRY(scan_exclusive_i64(ctx, st.totals, new_off, nb, new_off + nb));
   if (n_below) KSH_TRY(scan_exclusive_i64(ctx, below, below, nb, below + nb));
   KSH_HIP(hipMemcpyAsync(ctx->h_pinned, new_off + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -955,8 +1107,6 @@ int ksh_spss_decode_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s
   if (!ctx || !d_offsets || !n_keys) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
   KSH_TRY(check_geom(g));
   KSH_TRY(check_spss(s));
-  if (n_buckets(g) > kMaxLdsBuckets)
-    return fail(KSH_INVALID_ARGUMENT, "decode supports n_bucket_bits <= 14 (got %d)", g->n_bucket_bits);
   KSH_HIP(hipSetDevice(ctx->device));
   return KSH_BY_KEY(g->key_bytes, decode_plan_t, ctx, g, s, canonical_flag, d_offsets, n_keys);
 }

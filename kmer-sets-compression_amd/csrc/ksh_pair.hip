@@ -1039,6 +1039,16 @@ int pair_weights_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sets, in
                    int64_t* weights) {
   (void)g;
   const int64_t n_segs = int64_t(n_pairs) * n_ids;
+  // the segment scratch grows as n_pairs x n_ids (2^N / 50 sampled buckets: 6.8 x 10^8 segments for 64 sets at
+  // N = 24): a longer pair list goes in chunks of pairs (the weights are per pair, so they come out the same)
+  constexpr int64_t kMaxWeightSegs = int64_t(1) << 25;
+  if (n_segs > kMaxWeightSegs && n_pairs > 1) {
+    const int32_t per = int32_t(std::max<int64_t>(1, kMaxWeightSegs / std::max<int32_t>(n_ids, 1)));
+    for (int32_t p0 = 0; p0 < n_pairs; p0 += per)
+      KSH_TRY(pair_weights_t<KeyT>(ctx, g, sets, n_sets, bucket_ids, n_ids, pairs + 2 * int64_t(p0),
+                                   std::min(per, n_pairs - p0), weights + p0));
+    return KSH_OK;
+  }
   // stage the descriptors
   const size_t desc_bytes = align256(size_t(n_sets) * sizeof(SetPtrs)) +
                             align256(size_t(n_ids) * 4) + align256(size_t(n_pairs) * 8) +
