@@ -510,6 +510,49 @@ int ksh_kss_stats(const ksh_kss* k, int64_t stats[8]);
  * device buffers (release with ksh_free). */
 int ksh_kss_get(const ksh_kss* k, int32_t i, int64_t** d_offsets, void** d_keys, int64_t* n_keys);
 
+/* ---- Membership queries over a KmerSetSet: which nodes' Get(i) hold each k-mer ----------------
+ * Column i of a row is Get(i).Contains(q) (kmer_set_set.h:433-454) for EVERY node i of the structure,
+ * not only the inputs (they are columns 0 .. n_inputs - 1).  q is in Get(i) iff some node j whose own
+ * set holds q is reachable from i (i itself included); the index keeps the ancestor closure of the
+ * DAG, so a row is the OR of anc[j] over the nodes j that hold q.
+ * Rows: W = ceil(n_nodes / 64) uint64 words per query, row-major in the caller's query order; bit
+ * i % 64 of word i / 64 is column i.  Rows are held in registers / LDS: at most 16 words, i.e.
+ * structures of more than 1024 nodes are refused (KSH_INVALID_ARGUMENT, by name).
+ * Queries are 2K-bit patterns as in ksh_set_contains.  canonicalize != 0 looks up min(q, rc(q)) (the
+ * call for a structure built with canonical = 1).  A pattern with bits at or above 2K is in no set:
+ * its row is all zeros (checked before canonicalising). */
+typedef struct ksh_kss_index ksh_kss_index;
+/* From a built structure: borrows its resident node sets (no decode, no copy) and its context.  The
+ * index must be destroyed before the ksh_kss.  KSH_FAILED_PRECONDITION for an owner-sharded build in
+ * which some node lives on another rank. */
+int ksh_kss_index_from_kss(const ksh_kss* k, ksh_kss_index** out);
+/* From node containers and the DAG (what KmerSetSet::Load has): decodes every node (the ordinary
+ * decode, any N up to 24) into index-owned sets allocated from ctx's pool.  children as CSR on the
+ * HOST: node i's children are child_ids[child_offsets[i] .. child_offsets[i + 1]).  KSH_INVALID_ARGUMENT
+ * for a child id out of range, a self edge, a cycle, a malformed geometry or container view, and
+ * n_nodes outside [1, 1024]; the DAG is checked before any device work.  The containers are only read
+ * during the call; ctx must outlive the index. */
+int ksh_kss_index_create(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* nodes, int32_t n_nodes,
+                         const int64_t* child_offsets, const int32_t* child_ids, int canonical,
+                         ksh_kss_index** out);
+/* d_rows[n * W] for the n patterns d_kmers[n] (device), enqueued on the context's stream (the join
+ * route synchronises it once per pass of 2^24 queries, for the pass's tile count).
+ * route: 0 auto, 1 per-query search, 2 bucket join.  Scratch: the context's arena. */
+int ksh_kss_index_query(ksh_kss_index* idx, const uint64_t* d_kmers, int64_t n, int canonicalize,
+                        int route, uint64_t* d_rows);
+/* n_nodes, W, and the bytes of the resident sets the index reads (offsets included). */
+int ksh_kss_index_info(const ksh_kss_index* idx, int32_t* n_nodes, int32_t* words_per_row,
+                       int64_t* resident_bytes);
+/* The routes the last query took, a mask of KSH_QROUTE_* (synchronises the stream). */
+enum {
+  KSH_QROUTE_SEARCH = 1 << 0,   /* per-query search                                            */
+  KSH_QROUTE_JOIN = 1 << 1,     /* bucket join                                                  */
+  KSH_QROUTE_OVERSIZE = 1 << 2, /* ... some node's slice outgrew the LDS stage: searched in HBM */
+  KSH_QROUTE_CHUNKED = 1 << 3   /* ... the batch took more than one pass of 2^24 queries        */
+};
+int ksh_kss_index_routes(const ksh_kss_index* idx, uint32_t* bits);
+int ksh_kss_index_destroy(ksh_kss_index* idx);
+
 #ifdef __cplusplus
 }
 #endif

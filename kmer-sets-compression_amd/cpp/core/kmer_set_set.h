@@ -262,6 +262,56 @@ class KmerSetSet {
   std::int64_t stats_[8] = {};
 };
 
+// Which nodes' Get(i) hold each k-mer, for every node i (no counterpart in the reference): the index
+// decodes the nodes of a KmerSetSet, constructed or Load()ed, once (ksh_kss_index_create), and answers
+// batches of queries on the device.  Query returns Words() uint64 per query, row-major; bit i % 64 of
+// word i / 64 is Get(i).Contains(kmer).  canonical = look up Canonical() of each k-mer (the call for a
+// structure built with canonical = true).  Lives on the calling thread's context (ksc::Ctx()).
+template <int K, int N, typename KeyType>
+class KmerSetSetIndex {
+ public:
+  explicit KmerSetSetIndex(const KmerSetSet<K, N, KeyType>& kss, bool canonical = true) {
+    const ksh_geom g = KmerSet<K, N, KeyType>::Geom();
+    std::vector<ksh_spss_view> views;
+    std::vector<std::int64_t> offsets{0};
+    std::vector<std::int32_t> ids;
+    for (int i = 0; i < kss.Size(); i++) {
+      views.push_back(kss.Node(i).View());
+      auto it = kss.Children().find(i);
+      if (it != kss.Children().end()) ids.insert(ids.end(), it->second.begin(), it->second.end());
+      offsets.push_back(static_cast<std::int64_t>(ids.size()));
+    }
+    ksc::Check(ksh_kss_index_create(ksc::Ctx(), &g, views.data(), static_cast<std::int32_t>(views.size()),
+                                    offsets.data(), ids.data(), canonical ? 1 : 0, &index_));
+    std::int32_t n = 0;
+    ksc::Check(ksh_kss_index_info(index_, &n, &words_, nullptr));
+  }
+  KmerSetSetIndex(const KmerSetSetIndex&) = delete;
+  KmerSetSetIndex& operator=(const KmerSetSetIndex&) = delete;
+  ~KmerSetSetIndex() {
+    if (index_) ksh_kss_index_destroy(index_);
+  }
+
+  int Words() const { return words_; }
+
+  std::vector<std::uint64_t> Query(const std::vector<Kmer<K>>& kmers, bool canonical) const {
+    std::vector<std::uint64_t> bits;
+    bits.reserve(kmers.size());
+    for (const Kmer<K>& kmer : kmers) bits.push_back(kmer.Bits());
+    if (bits.empty()) return {};
+    const ksc::DeviceBuffer d_kmers = ksc::DeviceBuffer::FromHost(bits);
+    ksc::DeviceBuffer d_rows(bits.size() * std::size_t(words_) * 8);
+    ksc::Check(ksh_kss_index_query(index_, static_cast<const std::uint64_t*>(d_kmers.get()),
+                                   static_cast<std::int64_t>(bits.size()), canonical ? 1 : 0, 0,
+                                   static_cast<std::uint64_t*>(d_rows.get())));
+    return d_rows.ToHost<std::uint64_t>(bits.size() * std::size_t(words_));
+  }
+
+ private:
+  ksh_kss_index* index_ = nullptr;
+  std::int32_t words_ = 0;
+};
+
 // Reconstructs sets from a dumped directory without loading every node
 // (lib/core/kmer_set_set.h:629-775).
 template <int K, int N, typename KeyType>

@@ -649,7 +649,8 @@ int launch_xor_keys(ksh_ctx* ctx, const ksh_set_view* s, unsigned blocks, unsign
 
 extern "C" {
 
-int ksh_version(void) { return 3; }  // 2: ksh_comm_fns::struct_size, lanes, encode routes; 3: ksh_spss_cover_*
+int ksh_version(void) { return 4; }  // 2: ksh_comm_fns::struct_size, lanes, encode routes; 3: ksh_spss_cover_*;
+                                     // 4: ksh_kss_index_*
 
 const char* ksh_last_error(void) { return g_last_error.c_str(); }
 

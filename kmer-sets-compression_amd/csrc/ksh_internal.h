@@ -189,6 +189,9 @@ void cover_launch_emit(hipStream_t st, const ksh_spss_view* in, const int64_t* i
                        const uint32_t* u_sid, const uint32_t* u_koff, const uint8_t* u_flip, const int64_t* str_start,
                        int k, int64_t n_bases, uint8_t* bytes);
 
+// The context and geometry a KmerSetSet was built on (ksh_kss.hip; the query index borrows both).
+int kss_context(const ksh_kss* k, ksh_ctx** ctx, ksh_geom* g);
+
 hipEvent_t timer_event(ksh_ctx* ctx, size_t* index);
 void free_plan(ksh_ctx* ctx);  // ksh_encode.hip
 

@@ -131,6 +131,12 @@ static void poison(ksh_kss* k, int rc) {
     if (alive(k)) poison((k), (expr)); \
   } while (0)
 
+int kss_context(const ksh_kss* k, ksh_ctx** ctx, ksh_geom* g) {
+  *ctx = k->ctx;
+  *g = k->g;
+  return KSH_OK;
+}
+
 static void free_set(ksh_ctx* ctx, KssSet* s) {
   pool_free(ctx, s->off);
   pool_free(ctx, s->keys);

@@ -173,6 +173,13 @@ def lib():
         "ksh_kss_initial_weights": (C.c_int, [vp, C.POINTER(C.POINTER(i64)), C.POINTER(i64)]),
         "ksh_kss_stats": (C.c_int, [vp, C.POINTER(i64)]),
         "ksh_kss_get": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]),
+        "ksh_kss_index_from_kss": (C.c_int, [vp, C.POINTER(vp)]),
+        "ksh_kss_index_create": (C.c_int, [vp, GP, C.POINTER(SpssView), i32, C.POINTER(i64), C.POINTER(i32), C.c_int,
+                                           C.POINTER(vp)]),
+        "ksh_kss_index_query": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp]),
+        "ksh_kss_index_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]),
+        "ksh_kss_index_routes": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+        "ksh_kss_index_destroy": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -895,6 +902,95 @@ class DeviceKmerSetSet:
             dev = self.ctx.device.index
             lib().ksh_free(dev, d_off)
             lib().ksh_free(dev, d_keys)
+
+
+QROUTE_SEARCH, QROUTE_JOIN, QROUTE_OVERSIZE, QROUTE_CHUNKED = 1, 2, 4, 8
+
+
+class KssIndex:
+    """ksh_kss_index: which nodes' Get(i) hold each query k-mer (kmer_set_set.h:433-454), for every node i."""
+
+    def __init__(self, ctx, h, keep, borrowed=None):
+        self.ctx, self.h, self._keep, self._borrowed = ctx, h, keep, borrowed
+        n, w, b = C.c_int32(), C.c_int32(), C.c_int64()
+        check(lib().ksh_kss_index_info(h, C.byref(n), C.byref(w), C.byref(b)))
+        self.n_nodes, self.words = n.value, w.value
+
+    @classmethod
+    def from_kss(cls, dkss):
+        """Borrows the resident node sets of a built DeviceKmerSetSet (kept alive by the index)."""
+        h = C.c_void_p()
+        check(lib().ksh_kss_index_from_kss(dkss.h, C.byref(h)))
+        return cls(dkss.ctx, h, dkss, borrowed=dkss)
+
+    def _handle(self):
+        """The live index; an index whose borrowed structure was closed is closed too (its node sets are gone)."""
+        if self._borrowed is not None and getattr(self._borrowed, "h", None) is None:
+            self.close()
+            raise KshError(KSH_FAILED_PRECONDITION, "the KmerSetSet this index borrows its node sets from is closed")
+        if not getattr(self, "h", None):
+            raise KshError(KSH_FAILED_PRECONDITION, "the index is closed")
+        return self.h
+
+    @classmethod
+    def from_nodes(cls, ctx, compacts, children, canonical=True):
+        """From node containers (DeviceSpss) and children lists (children[i] = node i's children, or a dict
+        {i: [...]} as KmerSetSet::Load has): the index decodes every node."""
+        n = len(compacts)
+        if isinstance(children, dict):
+            children = [children.get(i, []) for i in range(n)]
+        offs = np.zeros(n + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([len(children[i]) for i in range(n)]) if n else []
+        ids = np.ascontiguousarray([c for i in range(n) for c in children[i]] or [0], dtype=np.int32)
+        views = (SpssView * max(n, 1))(*[c.view() for c in compacts])
+        h = C.c_void_p()
+        check(lib().ksh_kss_index_create(ctx.h, C.byref(compacts[0].g if n else Geom()), views, n,
+                                          offs.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          ids.ctypes.data_as(C.POINTER(C.c_int32)), int(canonical), C.byref(h)))
+        return cls(ctx, h, list(compacts))
+
+    def query(self, kmers, canonicalize=True, route=0, packed=False):
+        """Rows for the 2K-bit patterns `kmers` (numpy, or a device torch tensor of int64/uint64): an n x n_nodes
+        bool array, or with packed=True the n x W uint64 rows (a device tensor stays on the device)."""
+        import torch
+
+        on_device = isinstance(kmers, torch.Tensor)
+        if on_device:
+            q = kmers.contiguous()
+            if q.dtype != torch.int64:
+                q = q.view(torch.int64) if q.element_size() == 8 else q.to(torch.int64)
+            q = q.to(self.ctx.device)
+        else:
+            q = torch.from_numpy(np.ascontiguousarray(kmers, dtype=np.uint64).view(np.int64).copy()).to(self.ctx.device)
+        n = q.numel()
+        rows = torch.empty((max(n, 1), self.words), dtype=torch.int64, device=self.ctx.device)
+        check(lib().ksh_kss_index_query(self._handle(), q.data_ptr() if n else None, n, int(bool(canonicalize)), int(route),
+                                        rows.data_ptr()))
+        rows = rows[:n]
+        if packed:
+            return rows if on_device else rows.cpu().numpy().view(np.uint64)
+        host = rows.cpu().numpy().view(np.uint64)
+        bits = np.unpackbits(host.view(np.uint8).reshape(n, self.words * 8), axis=1, bitorder="little")
+        return bits[:, : self.n_nodes].astype(bool)
+
+    def routes(self):
+        bits = C.c_uint32()
+        check(lib().ksh_kss_index_routes(self._handle(), C.byref(bits)))
+        return bits.value
+
+    def info(self):
+        n, w, b = C.c_int32(), C.c_int32(), C.c_int64()
+        check(lib().ksh_kss_index_info(self._handle(), C.byref(n), C.byref(w), C.byref(b)))
+        return {"n_nodes": n.value, "words_per_row": w.value, "resident_bytes": b.value}
+
+    def close(self):
+        # (once its context is closed, the index's buffers went with the context's pool)
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            lib().ksh_kss_index_destroy(self.h)
+        self.h = None
+        self._keep = self._borrowed = None
+
+    __del__ = close
 
 
 class Comm:
