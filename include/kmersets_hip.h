@@ -330,7 +330,8 @@ enum {
   KSH_ROUTE_MATCH_MORE_ROUNDS = 1 << 14, /* the matching needed more than its first batch of rounds */
   KSH_ROUTE_FWD_TARGETS = 1 << 15,       /* k_adj_fwd_targets: forward probes marked at their targets, one search per k-mer */
   KSH_ROUTE_RC1_STREAMED = 1 << 16,      /* k_adj_rc1: k_adj_rc turned round (a group's records in LDS, its ranges streamed) */
-  KSH_ROUTE_RC_MARKS_GROUPS = 1 << 17    /* ... and k_adj_rc ran for some group whose records did not fit k_adj_rc1 */
+  KSH_ROUTE_RC_MARKS_GROUPS = 1 << 17,   /* ... and k_adj_rc ran for some group whose records did not fit k_adj_rc1 */
+  KSH_ROUTE_TGT_PARTS = 1 << 18          /* k_tgt_split / k_tgt_subcuts cut some window of k_adj_fwd_targets into parts */
 };
 int ksh_spss_encode_routes(ksh_ctx* ctx, int64_t* routes);
 /* Frees the current plan's device memory (also done by the next plan / ctx_destroy). */

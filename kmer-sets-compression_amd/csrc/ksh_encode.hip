@@ -2693,7 +2693,7 @@ __global__ __launch_bounds__(256) void k_edges(DevSet<KeyT> set, int64_t n_verti
     out[c] = 2 * u2 + side2;
   };
   if (side) {
-    set.for_group4(kmer_next(o, k, 0), [&](int64_t i) { take(int(uint64_t(set.keys[i]) & 3), i, true); });
+    set.for_group4(kmer_next(o, k, 0), [&](int64_t i) { take(set.last_base(i), i, true); });
     if (!directed) {
 #pragma unroll
       for (int c = 0; c < 4; c++) {
@@ -2717,7 +2717,7 @@ __global__ __launch_bounds__(256) void k_edges(DevSet<KeyT> set, int64_t n_verti
       // rc(Prev(o, c)) = Next(rc(o), 3 - c); a member is the canonical form of its candidate only when it is the smaller
       const uint64_t ro = revcomp(o, k);
       set.for_group4(kmer_next(ro, k, 0), [&](int64_t i) {
-        const int c = 3 - int(uint64_t(set.keys[i]) & 3);
+        const int c = 3 - set.last_base(i);
         const uint64_t y = kmer_prev(o, k, c);
         if (revcomp(y, k) < y) take(c, i, false);
       });
@@ -4272,6 +4272,7 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
     const char* tail = reinterpret_cast<const char*>(ctx->h_pinned);
     const auto at_tail = [&](size_t member_off) { return tail + (member_off - offsetof(EncCtl, t2)); };
     if (*reinterpret_cast<const int*>(at_tail(offsetof(EncCtl, rc_batched)))) p->routes |= KSH_ROUTE_RC_BATCHED;
+    if (*reinterpret_cast<const int*>(at_tail(offsetof(EncCtl, tgt_extra))) > 0) p->routes |= KSH_ROUTE_TGT_PARTS;
     const unsigned int* lc = reinterpret_cast<const unsigned int*>(at_tail(offsetof(EncCtl, long_count)));
     if (!p->stamped && (lc[0] || lc[1])) p->routes |= KSH_ROUTE_LONG_STRETCHES;
     if (p->rounds > kMatchFirst) p->routes |= KSH_ROUTE_MATCH_MORE_ROUNDS;

@@ -110,8 +110,17 @@ struct DevSet {
 
   // The members among the four consecutive k-mers g0 .. g0 + 3 (g0 ends in base A: they share
   // a bucket and, slices being at least four values wide, a slice): f(index) for each, ascending.
+  // With one key bit (N = 2K - 1) the four span two buckets: four single probes.
   template <typename F>
   __device__ __forceinline__ void for_group4(uint64_t g0, F f) const {
+    if (key_bits < 2) {
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        const int64_t idx = find(g0 + uint64_t(c));
+        if (idx >= 0) f(idx);
+      }
+      return;
+    }
     const int64_t b = int64_t(g0 >> key_bits);
     const KeyT gkey = KeyT(g0 & key_mask());
     int64_t lo, hi;
@@ -140,6 +149,12 @@ struct DevSet {
       if (uint64_t(keys[idx]) - uint64_t(gkey) >= 4) break;
       f(idx);
     }
+  }
+
+  // The last base of the k-mer at index t: the key's low two bits, or with one key bit the bucket's
+  // low bit and the key.
+  __device__ __forceinline__ int last_base(int64_t t) const {
+    return key_bits >= 2 ? int(uint64_t(keys[t]) & 3) : int(kmer(t) & 3);
   }
 
   // Bucket holding index t (largest b with off[b] <= t).
