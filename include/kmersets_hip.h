@@ -131,6 +131,62 @@ int ksh_ctx_set_lanes(ksh_ctx* ctx, int n_lanes);
 int ksh_ctx_mem_stats(ksh_ctx* ctx, int64_t stats[6], int reset_peak);
 int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
 
+/* ---- Plans -----------------------------------------------------------------------------------
+ * Eight operations take two calls: a *_plan call sizes the output and leaves a plan inside the context, the
+ * caller allocates, a *_write call consumes the plan.  The plans live in four groups, one pending plan per group
+ * and context:
+ *     pair   : ksh_pair_plan -> ksh_pair_write             ksh_set_union_plan -> ksh_set_union_write
+ *     decode : ksh_spss_decode_plan -> ksh_spss_decode_write, or -> ksh_kmer_count_write
+ *     encode : ksh_spss_encode_plan -> ksh_spss_encode_write   ksh_spss_cover_plan -> ksh_spss_cover_write
+ *     text   : ksh_spss_from_text_plan -> ksh_spss_from_text_write     ksh_fasta_plan -> ksh_fasta_write
+ * After a successful plan, and whatever was called in between, the write has exactly two outcomes:
+ *     exact   : KSH_OK, and the outputs are the true result;
+ *     refused : KSH_FAILED_PRECONDITION with a message that names the write and the plan it misses.  No output
+ *               buffer is touched, nothing is launched, and the context stays usable: a fresh plan + write on it
+ *               gives the true result.
+ * It is never KSH_OK with anything else, and never a write sized by another plan.
+ * The four writes that name no input -- ksh_spss_encode_write, ksh_spss_cover_write, ksh_spss_from_text_write,
+ * ksh_fasta_write -- have two forms.  The `_for` form states the plan the caller means: the sizes its buffers were
+ * allocated for (n_strings, n_bases as the plan returned them) and d_input, the device pointer the plan was given
+ * (set->d_offsets, unitigs->d_words, d_text); a plan of the same kind that replaced it is told apart by these, and
+ * the write is refused.  (A re-plan of the SAME input that returns the same sizes -- another mode or fast flag --
+ * is not told apart: it is served.)  The plain form has nothing to compare, so it serves a plan only where there
+ * can be no doubt: once, and not a plan that replaced an unwritten plan of its own kind -- the buffers may be sized
+ * for either of the two: that refusal ends the plan, so that the next plan + write is served; or use `_for`.
+ *
+ * What ends a pending plan (its write is refused afterwards), per call issued on the SAME context:
+ *     a plan call of the same group, successful, abandoned or failed     that group
+ *     ksh_kss_build, ksh_kss_build_sharded, ksh_kss_build_owned           pair, decode, encode (the build plans on
+ *                                                                         the context for itself; which of its jobs
+ *                                                                         run there depends on lanes and memory, so
+ *                                                                         it ends all three when it starts)
+ *     ksh_kss_get                                                         pair (its unions)
+ *     ksh_kss_index_create                                                decode (its decodes)
+ *     ksh_spss_encode_release, ksh_spss_cover_release                     encode
+ *     ksh_spss_decode_write, ksh_kmer_count_write                         decode (the write consumes its plan)
+ * Every other call leaves every pending plan exact: hash, contains, kmers, diff, ksh_pair_weights,
+ * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
+ * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
+ * calls, ksh_ctx_set_lanes, ksh_kss_index_query and the accessors of a ksh_kss / ksh_kss_index, plans and writes
+ * of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
+ * plan: nothing else uses their slot.
+ *
+ * A failed plan ends the older plan of its group (it has overwritten the group's scratch) and leaves none: the
+ * write after it is refused.
+ * Mismatched writes are refused on the host before any launch: a geometry (k, N, key bytes), canonical flag,
+ * container, set or -- for the decode -- d_offsets buffer other than the planned one; ksh_pair_write on a union
+ * plan and ksh_set_union_write on a pair plan; ksh_spss_encode_write on a cover plan and the reverse; n_strings,
+ * n_bases or d_input of a `_for` write other than the pending plan's; a write on a context other than the one
+ * that planned.  The plan stays pending for the right write.
+ * Replay: a second write on one plan is exact for the pair and union plans and for the `_for` writes of the
+ * encode, cover, text and FASTA plans (the write leaves the plan as it is; outputs may be skipped or repeated),
+ * and refused for the decode plan (ksh_spss_decode_write and ksh_kmer_count_write consume it) and for the plain
+ * encode, cover, text and FASTA writes, the same way every time.  A write after ksh_spss_encode_release /
+ * ksh_spss_cover_release is refused.
+ * Identity of a planned input is by pointer and size: freeing a planned input and allocating another one at the
+ * same address between the plan and the write is the caller's error and is not detected.  The inputs must stay
+ * alive and unchanged until the write.  Contexts are not thread-safe (above). */
+
 /* ---- KmerSet::Size / Hash  (lib/core/kmer_set.h:65-71, :224-244) --------------------- */
 /* XOR of all k-mer bit patterns in the set. */
 int ksh_set_hash(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* s, uint64_t* hash);
@@ -156,8 +212,8 @@ int ksh_dsu_components(ksh_ctx* ctx, int64_t n, const int32_t* d_x, const int32_
  *      A&B, A\B and B\A of one pair, lib/core/kmer_set_set.h:339-343) ------------------ */
 /* Pass 1.  Counts |A & B| per bucket and derives the bucket offsets of the three
  * results: d_off_i / d_off_amb / d_off_bma are int64[2^N + 1] outputs.
- * totals = { |A & B|, |A \ B|, |B \ A| } (host).  The plan stays valid for the
- * next ksh_pair_write on the same context with the same A and B. */
+ * totals = { |A & B|, |A \ B|, |B \ A| } (host).  The plan stays pending for ksh_pair_write on the same
+ * context with the same geometry, A and B (see "Plans" above). */
 int ksh_pair_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const ksh_set_view* b,
                   int64_t* d_off_i, int64_t* d_off_amb, int64_t* d_off_bma, int64_t totals[3]);
 /* Pass 2.  Writes the keys of the three results (buffers sized from `totals`;
@@ -255,6 +311,8 @@ int ksh_spss_to_text(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, ch
 int ksh_spss_from_text_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t n_bytes,
                             int64_t* n_strings, int64_t* n_bases);
 int ksh_spss_from_text_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens);
+int ksh_spss_from_text_write_for(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, int64_t n_strings, int64_t n_bases,
+                            const void* d_input);
 
 /* ---- KmerCounter: FASTA -> counted k-mers -> KmerSet (the step before the loop) ---------------
  * lib/core/kmer_counter.h:136-206 FromFASTA (lines 0, 2, ... are headers starting with '>',
@@ -273,6 +331,8 @@ int ksh_spss_from_text_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens);
 int ksh_fasta_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t n_bytes,
                    int64_t* n_fragments, int64_t* n_bases);
 int ksh_fasta_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens);
+int ksh_fasta_write_for(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, int64_t n_strings, int64_t n_bases,
+                   const void* d_input);
 int ksh_kmer_count_write(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* reads, int canonical,
                          int32_t cutoff, int64_t* d_offsets, void* d_keys, int64_t* n_keys,
                          int64_t* n_cut);
@@ -308,6 +368,8 @@ int ksh_svb_decode_0124(ksh_ctx* ctx, const uint8_t* d_in, int64_t n, uint32_t* 
 int ksh_spss_encode_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* set, int canonical,
                          int mode, int64_t* n_strings, int64_t* n_bases);
 int ksh_spss_encode_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens);
+int ksh_spss_encode_write_for(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, int64_t n_strings, int64_t n_bases,
+                         const void* d_input);
 /* stats = { unitigs, matching rounds, strings, bases } of the current plan. */
 int ksh_spss_encode_stats(ksh_ctx* ctx, int64_t stats[4]);
 /* Which variants of the encode's kernels the current plan ran (they are chosen by set size and geometry;
@@ -370,6 +432,8 @@ int ksh_spss_encode_release(ksh_ctx* ctx);
 int ksh_spss_cover_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* unitigs, int canonical, int fast,
                         int64_t* n_strings, int64_t* n_bases);
 int ksh_spss_cover_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens);
+int ksh_spss_cover_write_for(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, int64_t n_strings, int64_t n_bases,
+                        const void* d_input);
 /* stats = { unitigs (input strings), matching rounds, strings, bases } of the current cover plan. */
 int ksh_spss_cover_stats(ksh_ctx* ctx, int64_t stats[4]);
 /* Frees the current plan (of either kind), as ksh_spss_encode_release does. */

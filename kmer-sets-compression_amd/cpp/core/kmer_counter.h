@@ -86,8 +86,8 @@ class KmerCounter {
     ksc::Check(ksh_fasta_plan(ksc::Ctx(), &g, static_cast<const char*>(d_text.get()),
                               static_cast<std::int64_t>(fasta_.size()), &n_frag, &n_bases));
     ksc::DeviceBuffer words(std::size_t((n_bases + 31) / 32) * 8), lens(std::size_t(n_frag) * 4);
-    ksc::Check(ksh_fasta_write(ksc::Ctx(), static_cast<std::uint64_t*>(words.get()),
-                               static_cast<std::uint32_t*>(lens.get())));
+    ksc::Check(ksh_fasta_write_for(ksc::Ctx(), static_cast<std::uint64_t*>(words.get()),
+                                   static_cast<std::uint32_t*>(lens.get()), n_frag, n_bases, d_text.get()));
     const ksh_spss_view v{static_cast<const std::uint64_t*>(words.get()),
                           static_cast<const std::uint32_t*>(lens.get()), n_frag, n_bases};
     std::int64_t n = 0, n_cut = 0;

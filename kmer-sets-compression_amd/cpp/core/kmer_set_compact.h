@@ -38,8 +38,9 @@ class KmerSetCompact {
                                     &c.n_bases_));
     c.words_ = ksc::DeviceBuffer(std::size_t((c.n_bases_ + 31) / 32) * 8);
     c.lens_ = ksc::DeviceBuffer(std::size_t(c.n_) * 4);
-    ksc::Check(ksh_spss_encode_write(ksc::Ctx(), static_cast<std::uint64_t*>(c.words_.get()),
-                                     static_cast<std::uint32_t*>(c.lens_.get())));
+    ksc::Check(ksh_spss_encode_write_for(ksc::Ctx(), static_cast<std::uint64_t*>(c.words_.get()),
+                                         static_cast<std::uint32_t*>(c.lens_.get()), c.n_, c.n_bases_,
+                                         v.d_offsets));
     ksc::Check(ksh_ctx_sync(ksc::Ctx()));
     ksc::Check(ksh_spss_encode_release(ksc::Ctx()));
     return c;
@@ -137,8 +138,9 @@ class KmerSetCompact {
                                        static_cast<std::int64_t>(text.size()), &c.n_, &c.n_bases_));
     c.words_ = ksc::DeviceBuffer(std::size_t((c.n_bases_ + 31) / 32) * 8);
     c.lens_ = ksc::DeviceBuffer(std::size_t(c.n_) * 4);
-    ksc::Check(ksh_spss_from_text_write(ksc::Ctx(), static_cast<std::uint64_t*>(c.words_.get()),
-                                        static_cast<std::uint32_t*>(c.lens_.get())));
+    ksc::Check(ksh_spss_from_text_write_for(ksc::Ctx(), static_cast<std::uint64_t*>(c.words_.get()),
+                                            static_cast<std::uint32_t*>(c.lens_.get()), c.n_, c.n_bases_,
+                                            d_text.get()));
     return c;
   }
 

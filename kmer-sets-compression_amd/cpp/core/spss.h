@@ -32,8 +32,8 @@ std::vector<std::string> Encode(const KmerSet<K, N, KeyType>& kmer_set, bool can
   std::int64_t n = 0, n_bases = 0;
   ksc::Check(ksh_spss_encode_plan(ksc::Ctx(), &g, &v, canonical ? 1 : 0, mode, &n, &n_bases));
   ksc::DeviceBuffer words(std::size_t((n_bases + 31) / 32) * 8), lens(std::size_t(n) * 4);
-  ksc::Check(ksh_spss_encode_write(ksc::Ctx(), static_cast<std::uint64_t*>(words.get()),
-                                   static_cast<std::uint32_t*>(lens.get())));
+  ksc::Check(ksh_spss_encode_write_for(ksc::Ctx(), static_cast<std::uint64_t*>(words.get()),
+                                       static_cast<std::uint32_t*>(lens.get()), n, n_bases, v.d_offsets));
   ksc::Check(ksh_ctx_sync(ksc::Ctx()));
   ksc::Check(ksh_spss_encode_release(ksc::Ctx()));
   return KmerSetCompact<K, N, KeyType>::FromDevice(std::move(words), std::move(lens), n, n_bases)
@@ -50,8 +50,8 @@ std::vector<std::string> Cover(const std::vector<std::string>& unitigs, bool can
   std::int64_t n = 0, n_bases = 0;
   ksc::Check(ksh_spss_cover_plan(ksc::Ctx(), &g, &v, canonical ? 1 : 0, fast ? 1 : 0, &n, &n_bases));
   ksc::DeviceBuffer words(std::size_t((n_bases + 31) / 32) * 8), lens(std::size_t(n) * 4);
-  ksc::Check(ksh_spss_cover_write(ksc::Ctx(), static_cast<std::uint64_t*>(words.get()),
-                                  static_cast<std::uint32_t*>(lens.get())));
+  ksc::Check(ksh_spss_cover_write_for(ksc::Ctx(), static_cast<std::uint64_t*>(words.get()),
+                                      static_cast<std::uint32_t*>(lens.get()), n, n_bases, v.d_words));
   ksc::Check(ksh_ctx_sync(ksc::Ctx()));
   ksc::Check(ksh_spss_cover_release(ksc::Ctx()));
   return KmerSetCompact<K, N, KeyType>::FromDevice(std::move(words), std::move(lens), n, n_bases).ToStrings(1);

@@ -828,11 +828,20 @@ template <typename KeyT>
 int decode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int canonical_flag,
                   int64_t* d_offsets, int64_t* n_keys) {
   const int64_t nb = n_buckets(g);
+  // the slot and the sizes below are overwritten from here on: an older plan is gone, whether this one succeeds or not
+  ctx->dec_valid = false;
+  const auto plan_done = [&](int64_t kmers) {
+    ctx->dec_kmers = kmers;
+    ctx->dec_geom = *g;
+    ctx->dec_canonical = canonical_flag != 0;
+    ctx->dec_view = *s;
+    ctx->dec_offsets = d_offsets;
+    ctx->dec_valid = true;
+  };
   if (s->n_strings == 0 || s->n_bases == 0) {
     KSH_HIP(hipMemsetAsync(d_offsets, 0, size_t(nb + 1) * 8, ctx->stream));
     *n_keys = 0;
-    ctx->dec_kmers = 0;
-    ctx->dec_src = s->d_words;
+    plan_done(0);
     return KSH_OK;
   }
   // the buckets and key bits the counting works on: the coarse geometry on the wide route
@@ -883,10 +892,29 @@ int decode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int c
     return fail(KSH_INVALID_ARGUMENT, "spss: sum of string lengths (%lld) != n_bases (%lld)",
                 (long long)ctx->h_pinned[1], (long long)s->n_bases);
   *n_keys = ctx->h_pinned[0];
-  ctx->dec_kmers = *n_keys;
   ctx->dec_words = n_words;
   ctx->dec_groups = groups;
-  ctx->dec_src = s->d_words;
+  plan_done(*n_keys);
+  return KSH_OK;
+}
+
+// The write's arguments against the pending plan, on the host, before anything is launched: the plan's histogram,
+// offsets and scratch layout depend on every one of them.  A plan serves ONE write (the sort leaves its unique
+// counts where the plan's totals were and may rewrite d_offsets): the write consumes it.
+int decode_claim_plan(ksh_ctx* ctx, const char* who, const ksh_geom* g, const ksh_spss_view* s, int canonical_flag,
+                      const int64_t* d_offsets) {
+  if (!ctx->dec_valid)
+    return fail(KSH_FAILED_PRECONDITION, "%s without a pending ksh_spss_decode_plan on this context (none made, "
+                                         "replaced, failed, or already written)", who);
+  const ksh_spss_view& v = ctx->dec_view;
+  if (v.d_words != s->d_words || v.d_lens != s->d_lens || v.n_strings != s->n_strings || v.n_bases != s->n_bases)
+    return fail(KSH_FAILED_PRECONDITION, "%s: the pending ksh_spss_decode_plan was made for another container", who);
+  if (!same_geom(ctx->dec_geom, *g) || ctx->dec_canonical != (canonical_flag != 0))
+    return fail(KSH_FAILED_PRECONDITION, "%s: the pending ksh_spss_decode_plan was made with another geometry "
+                                         "(k, N, key bytes) or canonical flag", who);
+  if (ctx->dec_offsets != d_offsets)
+    return fail(KSH_FAILED_PRECONDITION, "%s: d_offsets is not the buffer the pending ksh_spss_decode_plan filled",
+                who);
   return KSH_OK;
 }
 
@@ -1021,8 +1049,7 @@ template <typename KeyT>
 int decode_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int canonical_flag,
                    int64_t* d_offsets, void* d_keys, int64_t* n_keys, int cutoff, int64_t* n_below) {
   const int64_t nb = n_buckets(g);
-  if (ctx->dec_src != s->d_words)
-    return fail(KSH_FAILED_PRECONDITION, "ksh_spss_decode_write without a matching decode_plan");
+  ctx->dec_valid = false;  // (claimed by the caller: decode_claim_plan)
   if (n_below) *n_below = 0;
   if (ctx->dec_kmers == 0) {
     *n_keys = 0;
@@ -1116,6 +1143,7 @@ int ksh_spss_decode_write(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* 
   if (!ctx || !d_offsets || !n_keys) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
   KSH_TRY(check_geom(g));
   KSH_TRY(check_spss(s));
+  KSH_TRY(decode_claim_plan(ctx, "ksh_spss_decode_write", g, s, canonical_flag, d_offsets));
   if (ctx->dec_kmers > 0 && !d_keys) return fail(KSH_INVALID_ARGUMENT, "d_keys is NULL");
   KSH_HIP(hipSetDevice(ctx->device));
   return KSH_BY_KEY(g->key_bytes, decode_write_t, ctx, g, s, canonical_flag, d_offsets, d_keys, n_keys, 1, nullptr);
@@ -1133,6 +1161,7 @@ int ksh_kmer_count_write(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* r
   KSH_TRY(check_spss(reads));
   if (cutoff < 0 || cutoff > 255) return fail(KSH_INVALID_ARGUMENT, "cutoff must be in 0..255 (uint8 counts)");
   if (cutoff < 1) cutoff = 1;  // "count < 0" never holds: a cutoff of 0 keeps every k-mer, like 1
+  KSH_TRY(decode_claim_plan(ctx, "ksh_kmer_count_write", g, reads, canonical_flag, d_offsets));
   if (ctx->dec_kmers > 0 && !d_keys) return fail(KSH_INVALID_ARGUMENT, "d_keys is NULL");
   KSH_HIP(hipSetDevice(ctx->device));
   return KSH_BY_KEY(g->key_bytes, decode_write_t, ctx, g, reads, canonical_flag, d_offsets, d_keys, n_keys, cutoff, n_cut);

@@ -3574,7 +3574,9 @@ struct EncPlan {
   bool cover = false;
   ksh_spss_view in{};
   int64_t* in_start = nullptr;  // base offset of every input string
-  bool cover_ready = false;     // the plan ran to its end: the write may read its arrays
+  bool ready = false;           // the plan (of either kind) ran to its end: the write may read its arrays
+  bool written = false;         // a write has served it
+  bool ambiguous = false;       // it replaced an unwritten plan of its own kind (claim_nameless)
 };
 
 inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
@@ -3654,6 +3656,16 @@ void free_plan(ksh_ctx* ctx) {
   if (p->ublock) pool_free(ctx, p->ublock);
   delete p;
   ctx->enc_state = nullptr;
+}
+
+// (asked before a new plan frees the current one)
+static bool replaces_unwritten(const ksh_ctx* ctx, bool cover) {
+  const EncPlan* o = static_cast<const EncPlan*>(ctx->enc_state);
+  return o && o->ready && !o->written && o->cover == cover;
+}
+
+void retire_plan(ksh_ctx* ctx) {
+  if (EncPlan* p = static_cast<EncPlan*>(ctx->enc_state)) p->ready = false;
 }
 
 // slices of about 1.5 keys (measured on 10^7- and 10^8-key sets: 9 and 12 bits are the
@@ -3762,15 +3774,18 @@ static int cover_stage(ksh_ctx* ctx, EncPlan* p, int64_t n_u, bool directed, boo
 template <typename KeyT>
 int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool directed, int mode,
                   int64_t* n_strings, int64_t* n_bases) {
+  const bool ambiguous = replaces_unwritten(ctx, false);
   free_plan(ctx);
   EncPlan* p = new EncPlan;
   ctx->enc_state = p;
+  p->ambiguous = ambiguous;
   p->g = *g;
   p->set = *sv;
   p->mode = mode;
   const int64_t n = sv->n_keys;
   p->n = n;
   if (n == 0) {
+    p->ready = true;
     *n_strings = 0;
     *n_bases = 0;
     return KSH_OK;
@@ -4280,6 +4295,7 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
   if (mode != 1) ns = (ctx->h_pinned[0] & 0xFFFFFFFF) + (ctx->h_pinned[0] >> 32) + ctx->h_pinned[1];
   p->n_strings = ns;
   p->n_bases = ctx->h_pinned[2];
+  p->ready = true;
   *n_strings = p->n_strings;
   *n_bases = p->n_bases;
   return KSH_OK;
@@ -4359,9 +4375,11 @@ int encode_write_t(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
 constexpr int64_t kCoverMaxStrings = (int64_t(1) << 30) - 1;
 int cover_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* in, bool directed, bool slow,
                int64_t* n_strings, int64_t* n_bases) {
+  const bool ambiguous = replaces_unwritten(ctx, true);
   free_plan(ctx);
   EncPlan* p = new EncPlan;
   ctx->enc_state = p;
+  p->ambiguous = ambiguous;
   p->cover = true;
   p->g = *g;
   p->in = *in;
@@ -4371,7 +4389,7 @@ int cover_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* in, bool di
   p->n = n;
   p->n_u = n;
   if (n == 0) {
-    p->cover_ready = true;
+    p->ready = true;
     *n_strings = 0;
     *n_bases = 0;
     return KSH_OK;
@@ -4464,7 +4482,7 @@ int cover_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* in, bool di
   if (walk_live_host[walk_rounds - 1]) return fail(KSH_INTERNAL, "the path cover still holds a loop");
   p->n_strings = (ctx->h_pinned[0] & 0xFFFFFFFF) + (ctx->h_pinned[0] >> 32) + ctx->h_pinned[1];
   p->n_bases = ctx->h_pinned[2];
-  p->cover_ready = true;
+  p->ready = true;
   *n_strings = p->n_strings;
   *n_bases = p->n_bases;
   return KSH_OK;
@@ -4507,14 +4525,36 @@ int ksh_spss_encode_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* se
   return KSH_BY_KEY(g->key_bytes, encode_plan_t, ctx, g, set, directed, mode, n_strings, n_bases);
 }
 
-int ksh_spss_encode_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+static int encode_write_entry(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, const PlanIdent* id) {
   if (!ctx) return fail(KSH_INVALID_ARGUMENT, "ctx is NULL");
   EncPlan* p = static_cast<EncPlan*>(ctx->enc_state);
   if (!p) return fail(KSH_FAILED_PRECONDITION, "ksh_spss_encode_write without ksh_spss_encode_plan");
-  if (p->cover) return fail(KSH_FAILED_PRECONDITION, "ksh_spss_encode_write: the current plan is a cover plan");
+  if (p->cover)
+    return fail(KSH_FAILED_PRECONDITION, "ksh_spss_encode_write without a pending ksh_spss_encode_plan: the current "
+                                         "plan is a cover plan");
+  if (!p->ready)
+    return fail(KSH_FAILED_PRECONDITION, "ksh_spss_encode_write without a pending ksh_spss_encode_plan: the current "
+                                         "one failed or was ended by a call that plans on the context itself");
+  bool end_plan = false;
+  const int claimed = claim_nameless("ksh_spss_encode_write", "ksh_spss_encode_plan", id, p->written, p->ambiguous,
+                                     p->n_strings, p->n_bases, p->set.d_offsets, &end_plan);
+  if (end_plan) p->ready = false;
+  KSH_TRY(claimed);
   if (p->n > 0 && (!d_words || !d_lens)) return fail(KSH_INVALID_ARGUMENT, "NULL output");
   KSH_HIP(hipSetDevice(ctx->device));
-  return KSH_BY_KEY(p->g.key_bytes, encode_write_t, ctx, d_words, d_lens);
+  KSH_TRY(KSH_BY_KEY(p->g.key_bytes, encode_write_t, ctx, d_words, d_lens));
+  p->written = true;
+  return KSH_OK;
+}
+
+int ksh_spss_encode_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+  return encode_write_entry(ctx, d_words, d_lens, nullptr);
+}
+
+int ksh_spss_encode_write_for(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, int64_t n_strings,
+                              int64_t n_bases, const void* d_input) {
+  const PlanIdent id{n_strings, n_bases, d_input};
+  return encode_write_entry(ctx, d_words, d_lens, &id);
 }
 
 int ksh_spss_encode_routes(ksh_ctx* ctx, int64_t* routes) {
@@ -4565,14 +4605,33 @@ int ksh_spss_cover_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* un
   return cover_plan(ctx, g, unitigs, !canonical, canonical && !fast, n_strings, n_bases);
 }
 
-int ksh_spss_cover_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+static int cover_write_entry(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, const PlanIdent* id) {
   if (!ctx) return fail(KSH_INVALID_ARGUMENT, "ctx is NULL");
   EncPlan* p = static_cast<EncPlan*>(ctx->enc_state);
   if (!p || !p->cover) return fail(KSH_FAILED_PRECONDITION, "ksh_spss_cover_write without ksh_spss_cover_plan");
-  if (!p->cover_ready) return fail(KSH_FAILED_PRECONDITION, "ksh_spss_cover_write after a failed ksh_spss_cover_plan");
+  if (!p->ready)
+    return fail(KSH_FAILED_PRECONDITION, "ksh_spss_cover_write without a pending ksh_spss_cover_plan: the current "
+                                         "one failed or was ended by a call that plans on the context itself");
+  bool end_plan = false;
+  const int claimed = claim_nameless("ksh_spss_cover_write", "ksh_spss_cover_plan", id, p->written, p->ambiguous,
+                                     p->n_strings, p->n_bases, p->in.d_words, &end_plan);
+  if (end_plan) p->ready = false;
+  KSH_TRY(claimed);
   if (p->n > 0 && (!d_words || !d_lens)) return fail(KSH_INVALID_ARGUMENT, "NULL output");
   KSH_HIP(hipSetDevice(ctx->device));
-  return cover_write(ctx, d_words, d_lens);
+  KSH_TRY(cover_write(ctx, d_words, d_lens));
+  p->written = true;
+  return KSH_OK;
+}
+
+int ksh_spss_cover_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+  return cover_write_entry(ctx, d_words, d_lens, nullptr);
+}
+
+int ksh_spss_cover_write_for(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, int64_t n_strings, int64_t n_bases,
+                             const void* d_input) {
+  const PlanIdent id{n_strings, n_bases, d_input};
+  return cover_write_entry(ctx, d_words, d_lens, &id);
 }
 
 int ksh_spss_cover_stats(ksh_ctx* ctx, int64_t stats[4]) {

@@ -232,13 +232,20 @@ int ksh_fasta_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t 
     ctx->fasta_plan = p;
     ctx->fasta_plan_free = [](void* q) { delete static_cast<FastaPlan*>(q); };
   }
+  // (a plain write cannot tell this plan from an unwritten one of its kind that it replaces: claim_nameless)
+  ctx->text_ambiguous = ctx->text_ready == 2 && !ctx->text_written;
+  ctx->text_written = false;
+  ctx->text_ready = 0;  // a pending plan of the group (text or FASTA) is gone, whether this one succeeds or not
   *p = FastaPlan();
   p->text = reinterpret_cast<const unsigned char*>(d_text);
   p->n_bytes = n_bytes;
   p->k = g->k;
   *n_fragments = 0;
   *n_bases = 0;
-  if (n_bytes == 0) return KSH_OK;  // no lines: an empty counter (std::getline yields nothing)
+  if (n_bytes == 0) {  // no lines: an empty counter (std::getline yields nothing)
+    ctx->text_ready = 2;
+    return KSH_OK;
+  }
   hipStream_t st = ctx->stream;
   const int64_t n_chunks = (n_bytes + kFaChunk - 1) / kFaChunk;
   const size_t per_chunk = fa256(size_t(n_chunks + 1) * 8);
@@ -272,7 +279,10 @@ int ksh_fasta_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t 
     return fail(KSH_FAILED_PRECONDITION, "FASTA files should have an even number of lines");
   if (*reinterpret_cast<int*>(ctx->h_pinned + 2) & 1) return fail(KSH_FAILED_PRECONDITION, "invalid FASTA file");
   p->n_frag = ctx->h_pinned[1];
-  if (p->n_frag == 0) return KSH_OK;
+  if (p->n_frag == 0) {
+    ctx->text_ready = 2;
+    return KSH_OK;
+  }
   // pass 2: fragments.  Their arrays go behind the per-chunk ones in the same slot; if that
   // makes the slot grow, its contents are lost and the two prefix arrays are recomputed (two
   // streaming passes).
@@ -317,16 +327,24 @@ int ksh_fasta_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t 
   if (ctx->h_pinned[2] != p->n_bases) return fail(KSH_INTERNAL, "fragment passes disagree on the base count");
   *n_fragments = p->n_kept;
   *n_bases = p->n_bases;
+  ctx->text_ready = 2;
   return KSH_OK;
 }
 
-int ksh_fasta_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+static int fasta_write_entry(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, const PlanIdent* id) {
   if (!ctx) return fail(KSH_INVALID_ARGUMENT, "ctx is NULL");
   FastaPlan* p = static_cast<FastaPlan*>(ctx->fasta_plan);
-  if (!p || (p->n_kept > 0 && ctx->text_slot_owner != 2))
-    return fail(KSH_FAILED_PRECONDITION, "ksh_fasta_write without ksh_fasta_plan");
+  if (!p || ctx->text_ready != 2 || (p->n_kept > 0 && ctx->text_slot_owner != 2))
+    return fail(KSH_FAILED_PRECONDITION, "ksh_fasta_write without a pending ksh_fasta_plan on this context (none "
+                                         "made, failed, or replaced by a text or FASTA plan)");
+  bool end_plan = false;
+  const int claimed = claim_nameless("ksh_fasta_write", "ksh_fasta_plan", id, ctx->text_written, ctx->text_ambiguous,
+                                     p->n_kept, p->n_bases, p->text, &end_plan);
+  if (end_plan) ctx->text_ready = 0;
+  KSH_TRY(claimed);
+  if (p->n_kept > 0 && (!d_words || !d_lens)) return fail(KSH_INVALID_ARGUMENT, "NULL output buffer");
+  ctx->text_written = true;
   if (p->n_kept == 0) return KSH_OK;
-  if (!d_words || !d_lens) return fail(KSH_INVALID_ARGUMENT, "NULL output buffer");
   hipStream_t st = ctx->stream;
   const int64_t n_chunks = (p->n_bytes + kFaChunk - 1) / kFaChunk;
   hipLaunchKernelGGL(k_fa_lens, dim3(fa_blocks(p->n_frag, 256)), dim3(256), 0, st, p->frag_start, p->frag_end,
@@ -337,6 +355,16 @@ int ksh_fasta_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
                      reinterpret_cast<unsigned long long*>(d_words));
   KSH_HIP(hipGetLastError());
   return KSH_OK;
+}
+
+int ksh_fasta_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+  return fasta_write_entry(ctx, d_words, d_lens, nullptr);
+}
+
+int ksh_fasta_write_for(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, int64_t n_strings, int64_t n_bases,
+                        const void* d_input) {
+  const PlanIdent id{n_strings, n_bases, d_input};
+  return fasta_write_entry(ctx, d_words, d_lens, &id);
 }
 
 }  // extern "C"

@@ -68,9 +68,14 @@ struct ksh_ctx {
   char* slot[3] = {nullptr, nullptr, nullptr};
   size_t slot_bytes[3] = {0, 0, 0};
 
-  // decode plan state
+  // decode plan state: what ksh_spss_decode_write / ksh_kmer_count_write compare their arguments with (dec_valid
+  // is cleared when a plan starts and when a write consumes it; include/kmersets_hip.h, "Plans")
   int64_t dec_words = 0, dec_groups = 0, dec_kmers = 0, dec_max_bucket = 0;
-  const void* dec_src = nullptr;
+  bool dec_valid = false;
+  ksh_geom dec_geom{};
+  int dec_canonical = 0;
+  ksh_spss_view dec_view{};
+  const void* dec_offsets = nullptr;
 
   // encode plan state (ksh_encode.hip)
   void* enc_state = nullptr;
@@ -86,14 +91,18 @@ struct ksh_ctx {
   void* fasta_plan = nullptr;
   void (*fasta_plan_free)(void*) = nullptr;
   int text_slot_owner = 0;  // 1: the text plan's arrays are in the slot, 2: the FASTA plan's
+  // the pending plan of the group: 0 none (cleared when a plan of either kind starts), 1 a text plan that ran to
+  // its end, 2 a FASTA plan that did; the writes ask for theirs
+  int text_ready = 0;
+  bool text_written = false, text_ambiguous = false;  // (as EncPlan::written / ambiguous, ksh_encode.hip)
 
   // pair plan (ksh_pair_plan -> ksh_pair_write)
   char* plan = nullptr;
   size_t plan_bytes = 0;
   int64_t plan_tiles = 0;
-  const void* plan_a_keys = nullptr;
-  const void* plan_b_keys = nullptr;
-  int64_t plan_buckets = 0;
+  int plan_kind = 0;  // kPlanNone, kPlanPair, kPlanUnion: cleared when a plan starts, set when it has succeeded
+  ksh_geom plan_geom{};
+  ksh_set_view plan_a{}, plan_b{};
 
   // chained scan (ksh_scan.h): the sums published by the workgroups of the running launch,
   // tagged with the launch's epoch
@@ -194,6 +203,63 @@ int kss_context(const ksh_kss* k, ksh_ctx** ctx, ksh_geom* g);
 
 hipEvent_t timer_event(ksh_ctx* ctx, size_t* index);
 void free_plan(ksh_ctx* ctx);  // ksh_encode.hip
+// The current encode / cover plan stays where it is (its memory goes when the next plan starts, as ever; stats and
+// routes stay readable) but serves no write any more.
+void retire_plan(ksh_ctx* ctx);  // ksh_encode.hip
+
+// Pending plans of a context (include/kmersets_hip.h, "Plans").  A composite call that runs pair plans, decodes or
+// encodes of its own on the caller's context drops the caller's pending plans of those groups when it starts, so
+// that their writes are refused whatever the composite call went on to do (lanes or not, merges or none).
+enum { kPlanNone = 0, kPlanPair = 1, kPlanUnion = 2 };
+enum { kGroupPair = 1, kGroupDecode = 2, kGroupEncode = 4 };
+inline void drop_plans(ksh_ctx* ctx, unsigned groups) {
+  if (groups & kGroupPair) ctx->plan_kind = kPlanNone;
+  if (groups & kGroupDecode) ctx->dec_valid = false;
+  if (groups & kGroupEncode) retire_plan(ctx);
+}
+// (on entry AND on return: what the composite call's own last plan left behind is no plan of the caller's either)
+struct BorrowedPlans {
+  ksh_ctx* ctx;
+  unsigned groups;
+  BorrowedPlans(ksh_ctx* c, unsigned g) : ctx(c), groups(g) { drop_plans(ctx, groups); }
+  ~BorrowedPlans() { drop_plans(ctx, groups); }
+  BorrowedPlans(const BorrowedPlans&) = delete;
+  BorrowedPlans& operator=(const BorrowedPlans&) = delete;
+};
+// The encode, cover, text and FASTA writes name no input.  The `_for` form states which plan the caller means:
+// the sizes its buffers were allocated for and the device pointer the plan was given.  The plain form serves a
+// plan only where that cannot be in doubt: once, and not when the plan replaced an unwritten plan of its own kind
+// (the caller's buffers may be sized for either of the two).
+struct PlanIdent {
+  int64_t n_strings, n_bases;
+  const void* d_input;
+};
+// *end_plan: the refusal ends the plan (an ambiguous one: the next plan then starts from a clean slate).
+inline int claim_nameless(const char* who, const char* plan, const PlanIdent* id, bool written, bool ambiguous,
+                          int64_t plan_strings, int64_t plan_bases, const void* plan_input, bool* end_plan) {
+  *end_plan = !id && !written && ambiguous;
+  if (!id) {
+    if (written)
+      return fail(KSH_FAILED_PRECONDITION, "%s without a pending %s: the current plan has been written (%s_for "
+                                           "writes a plan again)", who, plan, who);
+    if (ambiguous)
+      return fail(KSH_FAILED_PRECONDITION, "%s: the pending %s replaced an unwritten plan of the same kind, and "
+                                           "this write does not say which of the two its buffers were sized for: "
+                                           "the plan ends here (plan again, or use %s_for)", who, plan, who);
+    return KSH_OK;
+  }
+  if (id->d_input != plan_input)
+    return fail(KSH_FAILED_PRECONDITION, "%s_for: the pending %s was made for another input (d_input is not the "
+                                         "pointer it was given)", who, plan);
+  if (id->n_strings != plan_strings || id->n_bases != plan_bases)
+    return fail(KSH_FAILED_PRECONDITION, "%s_for: the buffers were sized for %lld strings and %lld bases, the "
+                                         "pending %s holds %lld and %lld", who, (long long)id->n_strings,
+                (long long)id->n_bases, plan, (long long)plan_strings, (long long)plan_bases);
+  return KSH_OK;
+}
+inline bool same_geom(const ksh_geom& a, const ksh_geom& b) {
+  return a.k == b.k && a.n_bucket_bits == b.n_bucket_bits && a.key_bytes == b.key_bytes;
+}
 
 struct Timer {
   ksh_ctx* ctx;

@@ -192,7 +192,7 @@ static int encode_set(ksh_ctx* ctx, const ksh_geom* g, const KssSet& s, int cano
   out->owned = true;
   int rc = pool_alloc(home, std::max<size_t>(size_t((nbases + 31) / 32) * 8, 16), reinterpret_cast<void**>(&out->words));
   if (rc == KSH_OK) rc = pool_alloc(home, std::max<size_t>(size_t(ns) * 4, 16), reinterpret_cast<void**>(&out->lens));
-  if (rc == KSH_OK) rc = ksh_spss_encode_write(ctx, out->words, out->lens);
+  if (rc == KSH_OK) rc = ksh_spss_encode_write_for(ctx, out->words, out->lens, ns, nbases, v.d_offsets);
   if (rc != KSH_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     free_compact(home, out);
@@ -1854,6 +1854,9 @@ int ksh_kss_build(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* inputs, 
   KSH_TRY(check_geom(g));
   if (n_inputs < 0 || n_ids < 0) return fail(KSH_INVALID_ARGUMENT, "negative count");
   KSH_HIP(hipSetDevice(ctx->device));
+  // the build runs pair plans, decodes and encodes of its own on ctx (which of them there and which on lanes
+  // depends on the lanes and the memory): the caller's pending plans of these groups end here, visibly
+  const BorrowedPlans borrowed(ctx, kGroupPair | kGroupDecode | kGroupEncode);
   ksh_kss* k = new ksh_kss;
   k->ctx = ctx;
   k->g = *g;
@@ -1889,6 +1892,9 @@ int ksh_kss_build_sharded(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* 
   if (world < 1 || rank < 0 || rank >= world) return fail(KSH_INVALID_ARGUMENT, "bad rank / world");
   if (world > 1 && !gather) return fail(KSH_INVALID_ARGUMENT, "a sharded build needs the all-gather callback");
   KSH_HIP(hipSetDevice(ctx->device));
+  // the build runs pair plans, decodes and encodes of its own on ctx (which of them there and which on lanes
+  // depends on the lanes and the memory): the caller's pending plans of these groups end here, visibly
+  const BorrowedPlans borrowed(ctx, kGroupPair | kGroupDecode | kGroupEncode);
   ksh_kss* k = new ksh_kss;
   k->ctx = ctx;
   k->g = *g;
@@ -1919,6 +1925,9 @@ int ksh_kss_build_owned(ksh_ctx* ctx, ksh_comm* comm, const ksh_geom* g, const k
   for (int32_t i = 0; i < n_inputs; i++)
     if (owners[i] < 0 || owners[i] >= world) return fail(KSH_INVALID_ARGUMENT, "owners[%d] = %d is no rank", i, owners[i]);
   KSH_HIP(hipSetDevice(ctx->device));
+  // the build runs pair plans, decodes and encodes of its own on ctx (which of them there and which on lanes
+  // depends on the lanes and the memory): the caller's pending plans of these groups end here, visibly
+  const BorrowedPlans borrowed(ctx, kGroupPair | kGroupDecode | kGroupEncode);
   ksh_kss* k = new ksh_kss;
   k->ctx = ctx;
   k->g = *g;
@@ -2100,6 +2109,7 @@ int ksh_kss_get(const ksh_kss* k, int32_t i, int64_t** d_offsets, void** d_keys,
   ksh_ctx* ctx = k->ctx;
   const ksh_geom* g = &k->g;
   KSH_HIP(hipSetDevice(ctx->device));
+  const BorrowedPlans borrowed(ctx, kGroupPair);  // (the union plans below)
   const int64_t nb = n_buckets(g);
   KssSet acc;
   KSH_TRY(alloc_offsets(ctx, g, &acc));

@@ -794,12 +794,44 @@ int check_view(const ksh_set_view* v, const char* name) {
   return KSH_OK;
 }
 
+// What a write compares its arguments with (host side, before the launch): the plan's kind -- the pair plan and the
+// union plan share ctx->plan and their writes read it in different modes --, the geometry (the tile count was
+// computed with the key width) and both operands.  Identity of an operand is by pointer and size.
+inline void plan_done(ksh_ctx* ctx, int kind, const ksh_geom* g, const ksh_set_view* a, const ksh_set_view* b,
+                      int64_t max_tiles) {
+  ctx->plan_tiles = max_tiles;
+  ctx->plan_geom = *g;
+  ctx->plan_a = *a;
+  ctx->plan_b = *b;
+  ctx->plan_kind = kind;
+}
+inline bool same_view(const ksh_set_view& x, const ksh_set_view& y) {
+  return x.d_offsets == y.d_offsets && x.d_keys == y.d_keys && x.n_keys == y.n_keys;
+}
+inline int plan_claim(ksh_ctx* ctx, int kind, const ksh_geom* g, const ksh_set_view* a, const ksh_set_view* b) {
+  const char* who = kind == kPlanPair ? "ksh_pair_write" : "ksh_set_union_write";
+  const char* plan = kind == kPlanPair ? "ksh_pair_plan" : "ksh_set_union_plan";
+  if (!ctx->plan || ctx->plan_kind == kPlanNone)
+    return fail(KSH_FAILED_PRECONDITION, "%s without a pending %s on this context (none made, replaced or failed)",
+                who, plan);
+  if (ctx->plan_kind != kind)
+    return fail(KSH_FAILED_PRECONDITION, "%s without a pending %s: the pending plan is a %s", who, plan,
+                ctx->plan_kind == kPlanPair ? "ksh_pair_plan" : "ksh_set_union_plan");
+  if (!same_geom(ctx->plan_geom, *g))
+    return fail(KSH_FAILED_PRECONDITION, "%s: the pending %s was made with another geometry (k, N, key bytes)", who,
+                plan);
+  if (!same_view(ctx->plan_a, *a) || !same_view(ctx->plan_b, *b))
+    return fail(KSH_FAILED_PRECONDITION, "%s: the pending %s was made for other sets", who, plan);
+  return KSH_OK;
+}
+
 template <typename KeyT>
 int pair_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const ksh_set_view* b,
                 int64_t* d_off_i, int64_t* d_off_amb, int64_t* d_off_bma, int64_t totals[3]) {
   const int64_t nb = n_buckets(g);
   const int64_t max_tiles = nb + (a->n_keys + b->n_keys) / TileCfg<KeyT>::kTile + 1;
   if (max_tiles > int64_t(0x7FFFFFF0)) return fail(KSH_INVALID_ARGUMENT, "pair too large for one launch");
+  ctx->plan_kind = kPlanNone;  // ctx->plan is overwritten (or moved) from here on, whether this plan succeeds or not
   KSH_TRY(plan_reserve(ctx, plan_bytes(nb, max_tiles)));
   KSH_TRY(arena_reserve(ctx, size_t(max_tiles / 256 + 4096) * 8 + (1u << 16)));
   arena_reset(ctx);
@@ -821,10 +853,7 @@ int pair_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const ks
   totals[0] = ctx->h_pinned[0];
   totals[1] = ctx->h_pinned[1];
   totals[2] = ctx->h_pinned[2];
-  ctx->plan_tiles = max_tiles;
-  ctx->plan_buckets = nb;
-  ctx->plan_a_keys = a->d_keys;
-  ctx->plan_b_keys = b->d_keys;
+  plan_done(ctx, kPlanPair, g, a, b, max_tiles);
   return KSH_OK;
 }
 
@@ -832,9 +861,7 @@ template <typename KeyT>
 int pair_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const ksh_set_view* b,
                  void* d_keys_i, void* d_keys_amb, void* d_keys_bma) {
   const int64_t nb = n_buckets(g);
-  if (!ctx->plan || ctx->plan_buckets != nb || ctx->plan_a_keys != a->d_keys ||
-      ctx->plan_b_keys != b->d_keys)
-    return fail(KSH_FAILED_PRECONDITION, "ksh_pair_write without a matching ksh_pair_plan");
+  KSH_TRY(plan_claim(ctx, kPlanPair, g, a, b));
   Plan p;
   plan_carve(ctx->plan, nb, ctx->plan_tiles, &p);
   {
@@ -971,6 +998,7 @@ int union_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const k
   const int64_t nb = n_buckets(g);
   const int64_t max_tiles = nb + (a->n_keys + b->n_keys) / TileCfg<KeyT>::kTile + 1;
   if (max_tiles > int64_t(0x7FFFFFF0)) return fail(KSH_INVALID_ARGUMENT, "pair too large for one launch");
+  ctx->plan_kind = kPlanNone;  // ctx->plan is overwritten (or moved) from here on, whether this plan succeeds or not
   KSH_TRY(plan_reserve(ctx, plan_bytes(nb, max_tiles)));
   KSH_TRY(arena_reserve(ctx, size_t(max_tiles / 256 + 4096) * 8 + (1u << 16)));
   arena_reset(ctx);
@@ -989,10 +1017,7 @@ int union_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const k
   KSH_HIP(hipMemcpyAsync(ctx->h_pinned, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   KSH_HIP(hipStreamSynchronize(ctx->stream));
   *total = ctx->h_pinned[0];
-  ctx->plan_tiles = max_tiles;
-  ctx->plan_buckets = nb;
-  ctx->plan_a_keys = a->d_keys;
-  ctx->plan_b_keys = b->d_keys;
+  plan_done(ctx, kPlanUnion, g, a, b, max_tiles);
   return KSH_OK;
 }
 
@@ -1000,9 +1025,7 @@ template <typename KeyT>
 int union_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const ksh_set_view* b,
                   void* d_keys_u) {
   const int64_t nb = n_buckets(g);
-  if (!ctx->plan || ctx->plan_buckets != nb || ctx->plan_a_keys != a->d_keys ||
-      ctx->plan_b_keys != b->d_keys)
-    return fail(KSH_FAILED_PRECONDITION, "ksh_set_union_write without a matching ksh_set_union_plan");
+  KSH_TRY(plan_claim(ctx, kPlanUnion, g, a, b));
   Plan p;
   plan_carve(ctx->plan, nb, ctx->plan_tiles, &p);
   launch_tile_merge<KeyT, 2>(ctx, p, nullptr, p.tile_ioff, p.split, static_cast<KeyT*>(d_keys_u),

@@ -446,6 +446,8 @@ int ksh_kss_index_create(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* n
     KSH_TRY(close_dag(n_nodes, child_offsets, child_ids, wt, &anc));
   }
   KSH_HIP(hipSetDevice(ctx->device));
+  // (the decodes below run on ctx: the caller's pending decode plan ends here)
+  const BorrowedPlans borrowed(ctx, kGroupDecode);
   auto* x = new ksh_kss_index;
   x->ctx = ctx;
   x->g = *g;

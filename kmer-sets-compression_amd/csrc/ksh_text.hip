@@ -252,13 +252,20 @@ int ksh_spss_from_text_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text,
     ctx->text_plan = p;
     ctx->text_plan_free = [](void* q) { delete static_cast<TextPlan*>(q); };
   }
+  // (a plain write cannot tell this plan from an unwritten one of its kind that it replaces: claim_nameless)
+  ctx->text_ambiguous = ctx->text_ready == 1 && !ctx->text_written;
+  ctx->text_written = false;
+  ctx->text_ready = 0;  // a pending plan of the group (text or FASTA) is gone, whether this one succeeds or not
   *p = TextPlan();
   p->text = reinterpret_cast<const unsigned char*>(d_text);
   p->n_bytes = n_bytes;
   p->k = g->k;
   *n_strings = 0;
   *n_bases = 0;
-  if (n_bytes == 0) return KSH_OK;
+  if (n_bytes == 0) {
+    ctx->text_ready = 1;
+    return KSH_OK;
+  }
   const int64_t n_chunks = (n_bytes + kChunk - 1) / kChunk;
   KSH_TRY(arena_reserve(ctx, size_t(n_chunks / 256 + 4096) * 8 + (1u << 16) + 512));
   arena_reset(ctx);
@@ -284,16 +291,24 @@ int ksh_spss_from_text_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text,
   p->n_bases = n_bytes - newlines;
   *n_strings = p->n_lines;
   *n_bases = p->n_bases;
+  ctx->text_ready = 1;
   return KSH_OK;
 }
 
-int ksh_spss_from_text_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+static int from_text_write_entry(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, const PlanIdent* id) {
   if (!ctx) return fail(KSH_INVALID_ARGUMENT, "ctx is NULL");
   TextPlan* p = static_cast<TextPlan*>(ctx->text_plan);
-  if (!p || (p->n_bytes > 0 && (!p->nl_before || ctx->text_slot_owner != 1)))
-    return fail(KSH_FAILED_PRECONDITION, "ksh_spss_from_text_write without ksh_spss_from_text_plan");
+  if (!p || ctx->text_ready != 1 || (p->n_bytes > 0 && (!p->nl_before || ctx->text_slot_owner != 1)))
+    return fail(KSH_FAILED_PRECONDITION, "ksh_spss_from_text_write without a pending ksh_spss_from_text_plan on this "
+                                         "context (none made, failed, or replaced by a text or FASTA plan)");
+  bool end_plan = false;
+  const int claimed = claim_nameless("ksh_spss_from_text_write", "ksh_spss_from_text_plan", id, ctx->text_written,
+                                     ctx->text_ambiguous, p->n_lines, p->n_bases, p->text, &end_plan);
+  if (end_plan) ctx->text_ready = 0;
+  KSH_TRY(claimed);
+  if (p->n_lines > 0 && (!d_words || !d_lens)) return fail(KSH_INVALID_ARGUMENT, "NULL output buffer");
+  ctx->text_written = true;
   if (p->n_lines == 0) return KSH_OK;
-  if (!d_words || !d_lens) return fail(KSH_INVALID_ARGUMENT, "NULL output buffer");
   const int64_t n_chunks = (p->n_bytes + kChunk - 1) / kChunk;
   KSH_TRY(arena_reserve(ctx, a256(size_t(p->n_lines) * 8) + 512));
   arena_reset(ctx);
@@ -315,6 +330,16 @@ int ksh_spss_from_text_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) 
   if (*reinterpret_cast<int*>(ctx->h_pinned) & 2)
     return fail(KSH_INVALID_ARGUMENT, "SPSS text holds a line shorter than K = %d", p->k);
   return KSH_OK;
+}
+
+int ksh_spss_from_text_write(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens) {
+  return from_text_write_entry(ctx, d_words, d_lens, nullptr);
+}
+
+int ksh_spss_from_text_write_for(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_lens, int64_t n_strings,
+                                 int64_t n_bases, const void* d_input) {
+  const PlanIdent id{n_strings, n_bases, d_input};
+  return from_text_write_entry(ctx, d_words, d_lens, &id);
 }
 
 }  // extern "C"

@@ -128,19 +128,23 @@ def lib():
                                             C.POINTER(i64)]),
         "ksh_fasta_plan": (C.c_int, [vp, GP, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "ksh_fasta_write": (C.c_int, [vp, vp, vp]),
+        "ksh_fasta_write_for": (C.c_int, [vp, vp, vp, i64, i64, vp]),
         "ksh_kmer_count_write": (C.c_int, [vp, GP, C.POINTER(SpssView), C.c_int, i32, vp, vp, C.POINTER(i64),
                                            C.POINTER(i64)]),
         "ksh_spss_to_text": (C.c_int, [vp, GP, C.POINTER(SpssView), vp]),
         "ksh_spss_from_text_plan": (C.c_int, [vp, GP, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "ksh_spss_from_text_write": (C.c_int, [vp, vp, vp]),
+        "ksh_spss_from_text_write_for": (C.c_int, [vp, vp, vp, i64, i64, vp]),
         "ksh_spss_encode_plan": (C.c_int, [vp, GP, SP, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(i64)]),
         "ksh_spss_encode_write": (C.c_int, [vp, vp, vp]),
+        "ksh_spss_encode_write_for": (C.c_int, [vp, vp, vp, i64, i64, vp]),
         "ksh_spss_encode_stats": (C.c_int, [vp, C.POINTER(i64)]),
         "ksh_spss_encode_routes": (C.c_int, [vp, C.POINTER(i64)]),
         "ksh_spss_encode_release": (C.c_int, [vp]),
         "ksh_spss_cover_plan": (C.c_int, [vp, GP, C.POINTER(SpssView), C.c_int, C.c_int, C.POINTER(i64),
                                           C.POINTER(i64)]),
         "ksh_spss_cover_write": (C.c_int, [vp, vp, vp]),
+        "ksh_spss_cover_write_for": (C.c_int, [vp, vp, vp, i64, i64, vp]),
         "ksh_spss_cover_stats": (C.c_int, [vp, C.POINTER(i64)]),
         "ksh_spss_cover_release": (C.c_int, [vp]),
         "ksh_set_union_plan": (C.c_int, [vp, GP, SP, SP, vp, C.POINTER(i64)]),
@@ -324,6 +328,15 @@ class DeviceSpss:
         return self.n_bases
 
 
+class Pending:
+    """What a plan-only wrapper of Context returns and the matching write-only wrapper takes: the plan's arguments
+    (kept alive) and the sizes it returned.  The plan itself lives inside the context (include/kmersets_hip.h,
+    "Plans")."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
 class BatchResult:
     """Results of Context.pair_algebra_batch: indexable / iterable as [(A & B, A \\ B, B \\ A), ...];
     the DeviceSet objects (slices of the two batch-wide allocations) are made on first access;
@@ -471,9 +484,9 @@ class Context:
                                   out_bma.offsets.data_ptr(), totals))
         return [int(x) for x in totals]
 
-    def pair_write(self, a, b, out_i, out_amb, out_bma):
+    def pair_write(self, a, b, out_i, out_amb, out_bma, g=None):
         va, vb = a.view(), b.view()
-        check(lib().ksh_pair_write(self.h, C.byref(a.g), C.byref(va), C.byref(vb),
+        check(lib().ksh_pair_write(self.h, C.byref(a.g if g is None else g), C.byref(va), C.byref(vb),
                                    out_i.keys.data_ptr() if out_i is not None else None,
                                    out_amb.keys.data_ptr() if out_amb is not None else None,
                                    out_bma.keys.data_ptr() if out_bma is not None else None))
@@ -498,52 +511,97 @@ class Context:
         check(lib().ksh_spss_size(self.h, C.byref(sp.g), C.byref(v), C.byref(out)))
         return out.value
 
-    def spss_decode(self, sp, canonical=True):
-        import torch
-
-        g = sp.g
-        out = DeviceSet.empty_like_offsets(g, 0, self.device)
+    def spss_decode_plan(self, sp, canonical=True):
+        """ksh_spss_decode_plan alone: a Pending with the container, the flag, `out` (a DeviceSet whose offsets
+        the plan filled, keys not yet allocated) and n_keys, the size of the key buffer the write needs."""
+        out = DeviceSet.empty_like_offsets(sp.g, 0, self.device)
         n = C.c_int64()
         v = sp.view()
-        check(lib().ksh_spss_decode_plan(self.h, C.byref(g), C.byref(v), int(canonical),
+        check(lib().ksh_spss_decode_plan(self.h, C.byref(sp.g), C.byref(v), int(canonical),
                                          out.offsets.data_ptr(), C.byref(n)))
-        out.keys = torch.empty(max(n.value * g.key_bytes, 16), dtype=torch.uint8, device=self.device)
-        check(lib().ksh_spss_decode_write(self.h, C.byref(g), C.byref(v), int(canonical),
-                                          out.offsets.data_ptr(), out.keys.data_ptr(), C.byref(n)))
-        out.n_keys = n.value
-        return out
+        return Pending(kind="decode", sp=sp, canonical=bool(canonical), out=out, n_keys=n.value)
 
-    # KmerCounter::FromFASTA / FromReads / ToKmerSet -------------------------------------------
-    def fasta_fragments(self, g, text):
-        """uint8 tensor (device) holding FASTA text -> DeviceSpss of the reads' ACGT fragments
-        of length >= K (what the counter counts k-mers of)."""
+    def _decode_keys(self, plan, keys):
         import torch
 
+        if keys is None:
+            keys = torch.empty(max(plan.n_keys * plan.sp.g.key_bytes, 16), dtype=torch.uint8, device=self.device)
+        plan.out.keys = keys
+        return keys
+
+    def spss_decode_write(self, plan, keys=None, g=None, canonical=None, sp=None):
+        """ksh_spss_decode_write on a Pending of spss_decode_plan (possibly one made on another Context).  keys: a
+        uint8 tensor of at least n_keys * key_bytes bytes (allocated when None); g / canonical / sp replace the
+        planned arguments (the library refuses a write whose arguments differ from the plan's)."""
+        keys = self._decode_keys(plan, keys)
+        g = plan.sp.g if g is None else g
+        v = (plan.sp if sp is None else sp).view()
+        n = C.c_int64()
+        check(lib().ksh_spss_decode_write(self.h, C.byref(g), C.byref(v),
+                                          int(plan.canonical if canonical is None else canonical),
+                                          plan.out.offsets.data_ptr(), keys.data_ptr(), C.byref(n)))
+        plan.out.n_keys = n.value
+        return plan.out
+
+    def kmer_count_write(self, plan, cutoff, keys=None, g=None, canonical=None):
+        """ksh_kmer_count_write on a Pending of spss_decode_plan: (DeviceSet of the k-mers seen >= cutoff times,
+        number of distinct k-mers below the cutoff)."""
+        keys = self._decode_keys(plan, keys)
+        g = plan.sp.g if g is None else g
+        v = plan.sp.view()
+        n, n_cut = C.c_int64(), C.c_int64()
+        check(lib().ksh_kmer_count_write(self.h, C.byref(g), C.byref(v),
+                                         int(plan.canonical if canonical is None else canonical), int(cutoff),
+                                         plan.out.offsets.data_ptr(), keys.data_ptr(), C.byref(n), C.byref(n_cut)))
+        plan.out.n_keys = n.value
+        return plan.out, n_cut.value
+
+    def spss_decode(self, sp, canonical=True):
+        return self.spss_decode_write(self.spss_decode_plan(sp, canonical))
+
+    # KmerCounter::FromFASTA / FromReads / ToKmerSet -------------------------------------------
+    def fasta_plan(self, g, text):
+        """ksh_fasta_plan alone: a Pending with n_strings (fragments) and n_bases."""
         n_frag, n_bases = C.c_int64(), C.c_int64()
         check(lib().ksh_fasta_plan(self.h, C.byref(g), text.data_ptr() if text.numel() else None,
                                    text.numel(), C.byref(n_frag), C.byref(n_bases)))
-        words = torch.zeros(max((n_bases.value + 31) // 32, 1), dtype=torch.int64, device=self.device)
-        lens = torch.zeros(max(n_frag.value, 1), dtype=torch.int32, device=self.device)
-        check(lib().ksh_fasta_write(self.h, words.data_ptr(), lens.data_ptr()))
-        return DeviceSpss(g, words, lens, n_frag.value, n_bases.value)
+        return Pending(kind="fasta", g=g, text=text, n_strings=n_frag.value, n_bases=n_bases.value)
+
+    def fasta_write(self, plan, words=None, lens=None, plain=False):
+        text = plan.text.data_ptr() if plan.text.numel() else None
+        return self._write_spss("ksh_fasta_write", plan, words, lens, text, plain, zero=True)
+
+    def fasta_fragments(self, g, text):
+        """uint8 tensor (device) holding FASTA text -> DeviceSpss of the reads' ACGT fragments
+        of length >= K (what the counter counts k-mers of)."""
+        return self.fasta_write(self.fasta_plan(g, text))
 
     def kmer_count(self, reads, cutoff, canonical=True):
         """(KmerSet of the k-mers seen >= cutoff times in the fragments, number of distinct
         k-mers below the cutoff)."""
+        return self.kmer_count_write(self.spss_decode_plan(reads, canonical), cutoff)
+
+    def _spss_buffers(self, plan, words, lens, zero=False):
+        """The output buffers of a container-producing write, sized from the plan (int64 words, int32 lens)."""
         import torch
 
-        g = reads.g
-        out = DeviceSet.empty_like_offsets(g, 0, self.device)
-        n, n_cut = C.c_int64(), C.c_int64()
-        v = reads.view()
-        check(lib().ksh_spss_decode_plan(self.h, C.byref(g), C.byref(v), int(canonical),
-                                         out.offsets.data_ptr(), C.byref(n)))
-        out.keys = torch.empty(max(n.value * g.key_bytes, 16), dtype=torch.uint8, device=self.device)
-        check(lib().ksh_kmer_count_write(self.h, C.byref(g), C.byref(v), int(canonical), int(cutoff),
-                                         out.offsets.data_ptr(), out.keys.data_ptr(), C.byref(n),
-                                         C.byref(n_cut)))
-        out.n_keys = n.value
-        return out, n_cut.value
+        make = torch.zeros if zero else torch.empty
+        if words is None:
+            words = make(max((plan.n_bases + 31) // 32, 1), dtype=torch.int64, device=self.device)
+        if lens is None:
+            lens = make(max(plan.n_strings, 1), dtype=torch.int32, device=self.device)
+        return words, lens
+
+    def _write_spss(self, name, plan, words, lens, d_input, plain, zero=False):
+        """One of the four writes that name no input, on a Pending of its plan: the `_for` form, which states the
+        plan it means (the planned sizes and input pointer), or with plain=True the three-argument form."""
+        words, lens = self._spss_buffers(plan, words, lens, zero=zero)
+        if plain:
+            check(getattr(lib(), name)(self.h, words.data_ptr(), lens.data_ptr()))
+        else:
+            check(getattr(lib(), name + "_for")(self.h, words.data_ptr(), lens.data_ptr(), plan.n_strings,
+                                                plan.n_bases, d_input))
+        return DeviceSpss(plan.g, words, lens, plan.n_strings, plan.n_bases)
 
     # KmerSetCompact::Dump / Load text (one string per line) ------------------------------
     def spss_to_text(self, sp):
@@ -555,33 +613,40 @@ class Context:
         check(lib().ksh_spss_to_text(self.h, C.byref(sp.g), C.byref(v), text.data_ptr() if text.numel() else None))
         return text
 
-    def spss_from_text(self, g, text):
-        """uint8 tensor (device) holding lines over ACGT -> DeviceSpss."""
-        import torch
-
+    def spss_from_text_plan(self, g, text):
+        """ksh_spss_from_text_plan alone: a Pending with n_strings and n_bases."""
         n_strings, n_bases = C.c_int64(), C.c_int64()
         check(lib().ksh_spss_from_text_plan(self.h, C.byref(g), text.data_ptr() if text.numel() else None,
                                             text.numel(), C.byref(n_strings), C.byref(n_bases)))
-        words = torch.empty(max((n_bases.value + 31) // 32, 1), dtype=torch.int64, device=self.device)
-        lens = torch.empty(max(n_strings.value, 1), dtype=torch.int32, device=self.device)
-        check(lib().ksh_spss_from_text_write(self.h, words.data_ptr(), lens.data_ptr()))
-        return DeviceSpss(g, words, lens, n_strings.value, n_bases.value)
+        return Pending(kind="from_text", g=g, text=text, n_strings=n_strings.value, n_bases=n_bases.value)
+
+    def spss_from_text_write(self, plan, words=None, lens=None, plain=False):
+        text = plan.text.data_ptr() if plan.text.numel() else None
+        return self._write_spss("ksh_spss_from_text_write", plan, words, lens, text, plain)
+
+    def spss_from_text(self, g, text):
+        """uint8 tensor (device) holding lines over ACGT -> DeviceSpss."""
+        return self.spss_from_text_write(self.spss_from_text_plan(g, text))
 
     # KmerSetCompact::FromKmerSet / GetUnitigsCanonical ---------------------------------------
-    def spss_encode(self, s, mode=0, canonical=True):
-        """mode 0: SPSS (GetSPSSCanonical fast, or GetSPSS when canonical is False); mode 1: unitigs;
-        mode 2: GetSPSSCanonical(fast = false).  Returns a DeviceSpss."""
-        import torch
-
+    def spss_encode_plan(self, s, mode=0, canonical=True):
+        """ksh_spss_encode_plan alone: a Pending with n_strings and n_bases."""
         ns, nbases = C.c_int64(), C.c_int64()
         v = s.view()
         check(lib().ksh_spss_encode_plan(self.h, C.byref(s.g), C.byref(v), int(canonical), mode,
                                          C.byref(ns), C.byref(nbases)))
-        n_words = (nbases.value + 31) // 32
-        words = torch.empty(max(n_words, 1), dtype=torch.int64, device=self.device)
-        lens = torch.empty(max(ns.value, 1), dtype=torch.int32, device=self.device)
-        check(lib().ksh_spss_encode_write(self.h, words.data_ptr(), lens.data_ptr()))
-        return DeviceSpss(s.g, words, lens, ns.value, nbases.value)
+        return Pending(kind="encode", g=s.g, set=s, n_strings=ns.value, n_bases=nbases.value)
+
+    def spss_encode_write(self, plan, words=None, lens=None, plain=False):
+        return self._write_spss("ksh_spss_encode_write", plan, words, lens, plan.set.pointers()[0], plain)
+
+    def spss_encode_release(self):
+        check(lib().ksh_spss_encode_release(self.h))
+
+    def spss_encode(self, s, mode=0, canonical=True):
+        """mode 0: SPSS (GetSPSSCanonical fast, or GetSPSS when canonical is False); mode 1: unitigs;
+        mode 2: GetSPSSCanonical(fast = false).  Returns a DeviceSpss."""
+        return self.spss_encode_write(self.spss_encode_plan(s, mode, canonical))
 
     def spss_encode_stats(self):
         st = (C.c_int64 * 4)()
@@ -589,20 +654,26 @@ class Context:
         return {"unitigs": st[0], "rounds": st[1], "strings": st[2], "bases": st[3]}
 
     # GetSPSSCanonical / GetSPSS from caller-supplied unitigs -----------------------------------
-    def spss_cover(self, unitigs, canonical=True, fast=True):
-        """The path cover of a DeviceSpss whose strings are unitigs (GetSPSSCanonical(unitigs, prefixes, suffixes,
-        fast), or GetSPSS(unitigs, prefixes) when canonical is False).  Returns a DeviceSpss; the input must
-        meet the preconditions of ksh_spss_cover_plan (include/kmersets_hip.h), else KshError."""
-        import torch
-
+    def spss_cover_plan(self, unitigs, canonical=True, fast=True):
+        """ksh_spss_cover_plan alone: a Pending with n_strings and n_bases (the input must stay alive until the
+        write)."""
         ns, nbases = C.c_int64(), C.c_int64()
         v = unitigs.view()
         check(lib().ksh_spss_cover_plan(self.h, C.byref(unitigs.g), C.byref(v), int(canonical), int(fast),
                                         C.byref(ns), C.byref(nbases)))
-        words = torch.empty(max((nbases.value + 31) // 32, 1), dtype=torch.int64, device=self.device)
-        lens = torch.empty(max(ns.value, 1), dtype=torch.int32, device=self.device)
-        check(lib().ksh_spss_cover_write(self.h, words.data_ptr(), lens.data_ptr()))
-        return DeviceSpss(unitigs.g, words, lens, ns.value, nbases.value)
+        return Pending(kind="cover", g=unitigs.g, unitigs=unitigs, n_strings=ns.value, n_bases=nbases.value)
+
+    def spss_cover_write(self, plan, words=None, lens=None, plain=False):
+        return self._write_spss("ksh_spss_cover_write", plan, words, lens, plan.unitigs.words.data_ptr(), plain)
+
+    def spss_cover_release(self):
+        check(lib().ksh_spss_cover_release(self.h))
+
+    def spss_cover(self, unitigs, canonical=True, fast=True):
+        """The path cover of a DeviceSpss whose strings are unitigs (GetSPSSCanonical(unitigs, prefixes, suffixes,
+        fast), or GetSPSS(unitigs, prefixes) when canonical is False).  Returns a DeviceSpss; the input must
+        meet the preconditions of ksh_spss_cover_plan (include/kmersets_hip.h), else KshError."""
+        return self.spss_cover_write(self.spss_cover_plan(unitigs, canonical, fast))
 
     def spss_cover_stats(self):
         st = (C.c_int64 * 4)()
@@ -701,21 +772,33 @@ class Context:
         check(lib().ksh_pair_algebra_batch(self.h, C.byref(g), C.cast(jobs.ctypes.data, C.POINTER(PairJob)), n))
         return BatchResult(g, off_rows, key_pool, starts, byte_caps, jobs[:, 12:15].tolist())
 
-    def set_union(self, a, b):
-        """KmerSet::Add: A | B as a new DeviceSet."""
-        import torch
-
-        g = a.g
-        out = DeviceSet.empty_like_offsets(g, 0, self.device)
+    def set_union_plan(self, a, b):
+        """ksh_set_union_plan alone: a Pending with the operands, `out` (offsets filled, keys not yet allocated)
+        and n_keys = |A | B|."""
+        out = DeviceSet.empty_like_offsets(a.g, 0, self.device)
         total = C.c_int64()
         va, vb = a.view(), b.view()
-        check(lib().ksh_set_union_plan(self.h, C.byref(g), C.byref(va), C.byref(vb),
+        check(lib().ksh_set_union_plan(self.h, C.byref(a.g), C.byref(va), C.byref(vb),
                                        out.offsets.data_ptr(), C.byref(total)))
         out.n_keys = total.value
-        out.keys = torch.empty(max(total.value * g.key_bytes, 16), dtype=torch.uint8, device=self.device)
-        check(lib().ksh_set_union_write(self.h, C.byref(g), C.byref(va), C.byref(vb),
-                                        out.keys.data_ptr()))
-        return out
+        return Pending(kind="union", a=a, b=b, out=out, n_keys=total.value)
+
+    def set_union_write(self, plan, keys=None, g=None):
+        """ksh_set_union_write on a Pending of set_union_plan; keys: a uint8 tensor of at least n_keys * key_bytes
+        bytes (allocated when None); g replaces the planned geometry (the library refuses the mismatch)."""
+        import torch
+
+        g = plan.a.g if g is None else g
+        if keys is None:
+            keys = torch.empty(max(plan.n_keys * g.key_bytes, 16), dtype=torch.uint8, device=self.device)
+        plan.out.keys = keys
+        va, vb = plan.a.view(), plan.b.view()
+        check(lib().ksh_set_union_write(self.h, C.byref(g), C.byref(va), C.byref(vb), keys.data_ptr()))
+        return plan.out
+
+    def set_union(self, a, b):
+        """KmerSet::Add: A | B as a new DeviceSet."""
+        return self.set_union_write(self.set_union_plan(a, b))
 
     def set_diff(self, a, b):
         out = C.c_int64()
