@@ -167,8 +167,8 @@ int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
  * Every other call leaves every pending plan exact: hash, contains, kmers, diff, ksh_pair_weights,
  * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
  * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
- * calls, ksh_ctx_set_lanes, ksh_kss_index_query and the accessors of a ksh_kss / ksh_kss_index, plans and writes
- * of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
+ * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits and the accessors of a ksh_kss / ksh_kss_index, plans
+ * and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
  * plan: nothing else uses their slot.
  *
  * A failed plan ends the older plan of its group (it has overwritten the group's scratch) and leaves none: the
@@ -608,15 +608,39 @@ int ksh_kss_index_query(ksh_kss_index* idx, const uint64_t* d_kmers, int64_t n, 
 /* n_nodes, W, and the bytes of the resident sets the index reads (offsets included). */
 int ksh_kss_index_info(const ksh_kss_index* idx, int32_t* n_nodes, int32_t* words_per_row,
                        int64_t* resident_bytes);
-/* The routes the last query took, a mask of KSH_QROUTE_* (synchronises the stream). */
+/* The routes the last query (ksh_kss_index_query or ksh_seq_hits) took, a mask of KSH_QROUTE_* (synchronises the
+ * stream). */
 enum {
-  KSH_QROUTE_SEARCH = 1 << 0,   /* per-query search                                            */
-  KSH_QROUTE_JOIN = 1 << 1,     /* bucket join                                                  */
-  KSH_QROUTE_OVERSIZE = 1 << 2, /* ... some node's slice outgrew the LDS stage: searched in HBM */
-  KSH_QROUTE_CHUNKED = 1 << 3   /* ... the batch took more than one pass of 2^24 queries        */
+  KSH_QROUTE_SEARCH = 1 << 0,    /* per-query search                                            */
+  KSH_QROUTE_JOIN = 1 << 1,      /* bucket join                                                  */
+  KSH_QROUTE_OVERSIZE = 1 << 2,  /* ... some node's slice outgrew the LDS stage: searched in HBM */
+  KSH_QROUTE_CHUNKED = 1 << 3,   /* ... the batch took more than one pass of 2^24 queries        */
+  KSH_QROUTE_SEQ_PASSES = 1 << 4 /* ksh_seq_hits: the batch took more than one pass of positions */
 };
 int ksh_kss_index_routes(const ksh_kss_index* idx, uint32_t* bits);
 int ksh_kss_index_destroy(ksh_kss_index* idx);
+
+/* ---- Sequence queries: k-mer hits per sequence and node ------------------------------------------
+ * d_hits[s * n_nodes + i] = number of k-mer positions p of sequence s (0 <= p <= lens[s]) whose k-mer is in
+ * Get(i), for every node i of the index.  Sequences: ksh_spss_view layout, as ksh_fasta_write,
+ * ksh_spss_from_text_write and ksh_spss_encode_write produce it.  Positions are counted, not distinct k-mers:
+ * a k-mer that occurs twice in a sequence counts twice.  Windows never cross from one string into the next.
+ * canonicalize and route: as in ksh_kss_index_query (the auto rule is applied to every pass).
+ * pass_positions: k-mer positions handled per pass; the k-mers and bit rows of a pass stay in scratch from the
+ * context's pool, 8 + 8 W bytes per position.  0: the default, which keeps that scratch within 256 MiB and a pass
+ * within the join's 2^24 queries (2^24 positions at W = 1, about 1.9 * 10^6 at W = 16).  Any value >= 1 is taken
+ * as it is (values above 2^28 as 2^28); a sequence longer than a pass is split across passes and its counts add
+ * up.  ksh_kss_index_routes reports the routes of all passes, and KSH_QROUTE_SEQ_PASSES when there were several.
+ * d_hits (n_strings * n_nodes values, device) is written in full, zeros included; n_strings == 0 is KSH_OK with
+ * nothing written.  Enqueued on the index's context stream; the stream is synchronised once for the size check
+ * and, on the join route, once per pass.
+ * KSH_INVALID_ARGUMENT, before anything is counted: a NULL argument, a negative size or pass_positions, a route
+ * outside 0..2, an index whose geometry has K < 4 (all before any device work); lens[s] == UINT32_MAX, or
+ * sum(lens + K) != n_bases (as the cover: checked on the device before the words are read).
+ * The index must be usable as for ksh_kss_index_query: one made by ksh_kss_index_from_kss borrows the node sets
+ * of its ksh_kss and must not be used after ksh_kss_destroy. */
+int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int canonicalize, int route,
+                 int64_t pass_positions, uint32_t* d_hits);
 
 #ifdef __cplusplus
 }

@@ -283,8 +283,7 @@ class KmerSetSetIndex {
     }
     ksc::Check(ksh_kss_index_create(ksc::Ctx(), &g, views.data(), static_cast<std::int32_t>(views.size()),
                                     offsets.data(), ids.data(), canonical ? 1 : 0, &index_));
-    std::int32_t n = 0;
-    ksc::Check(ksh_kss_index_info(index_, &n, &words_, nullptr));
+    ksc::Check(ksh_kss_index_info(index_, &nodes_, &words_, nullptr));
   }
   KmerSetSetIndex(const KmerSetSetIndex&) = delete;
   KmerSetSetIndex& operator=(const KmerSetSetIndex&) = delete;
@@ -307,9 +306,27 @@ class KmerSetSetIndex {
     return d_rows.ToHost<std::uint64_t>(bits.size() * std::size_t(words_));
   }
 
+  int Nodes() const { return nodes_; }
+
+  // Hits per sequence and node (ksh_seq_hits): element s * Nodes() + i is the number of k-mer positions of
+  // string s of `sequences` whose k-mer -- its Canonical() with canonical = true -- is in Get(i).  A k-mer
+  // that occurs twice in a string counts twice.
+  std::vector<std::uint32_t> CountHits(const KmerSetCompact<K, N, KeyType>& sequences, bool canonical) const {
+    const std::size_t cells = std::size_t(sequences.StringCount()) * std::size_t(nodes_);
+    if (cells == 0) return {};
+    const ksh_spss_view v = sequences.View();
+    ksc::DeviceBuffer d_hits(cells * 4);
+    ksc::Check(ksh_seq_hits(&v, index_, canonical ? 1 : 0, 0, 0, static_cast<std::uint32_t*>(d_hits.get())));
+    return d_hits.ToHost<std::uint32_t>(cells);
+  }
+  // The same for strings over ACGT, each at least K long.
+  std::vector<std::uint32_t> CountHits(const std::vector<std::string>& sequences, bool canonical) const {
+    return CountHits(KmerSetCompact<K, N, KeyType>::FromStrings(sequences), canonical);
+  }
+
  private:
   ksh_kss_index* index_ = nullptr;
-  std::int32_t words_ = 0;
+  std::int32_t words_ = 0, nodes_ = 0;
 };
 
 // Reconstructs sets from a dumped directory without loading every node

@@ -201,6 +201,20 @@ void cover_launch_emit(hipStream_t st, const ksh_spss_view* in, const int64_t* i
 // The context and geometry a KmerSetSet was built on (ksh_kss.hip; the query index borrows both).
 int kss_context(const ksh_kss* k, ksh_ctx** ctx, ksh_geom* g);
 
+// What ksh_seq_hits (ksh_seqhits.hip) needs of a query index (ksh_query.hip): its shape, the auto rule of
+// ksh_kss_index_query for a batch of n, one look-up of n patterns on the search or the join route (rows in the
+// patterns' order; it leaves the index's route bits alone), and the route bits ksh_kss_index_routes reports.
+struct IndexShape {
+  ksh_ctx* ctx;
+  ksh_geom g;
+  int32_t n_nodes, words, wt;  // wt: words padded to a power of two (the look-up kernels' template width)
+  int* d_flags;
+};
+IndexShape index_shape(const ksh_kss_index* idx);
+bool index_auto_joins(const ksh_kss_index* idx, int64_t n);
+int index_lookup(ksh_kss_index* idx, bool join, const uint64_t* d_kmers, int64_t n, int canon, uint64_t* d_rows);
+void index_set_routes(ksh_kss_index* idx, uint32_t routes);
+
 hipEvent_t timer_event(ksh_ctx* ctx, size_t* index);
 void free_plan(ksh_ctx* ctx);  // ksh_encode.hip
 // The current encode / cover plan stays where it is (its memory goes when the next plan starts, as ever; stats and

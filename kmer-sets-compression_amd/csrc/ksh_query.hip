@@ -306,6 +306,27 @@ int dispatch(ksh_kss_index* x, bool join, const uint64_t* d_kmers, int64_t n, in
 #undef KSH_Q_W
 }
 
+// auto: the join streams every touched slice once; the search costs each query about one 64-byte
+// sector per node (the upper levels of its searches hit the cache).  Join once the search's sectors
+// would outweigh one pass over the resident keys, and the batch fills the buckets: a join tile walks
+// every node with two barriers whatever it holds, so at one query per tile the search is cheaper.
+// Keys that fit the Infinity Cache serve the search's sectors from the cache: search.
+bool index_auto_joins(const ksh_kss_index* idx, int64_t n) {
+  const double key_bytes = double(idx->total_keys) * idx->g.key_bytes;
+  return key_bytes > double(kCacheBytes) && double(n) * idx->n_nodes * 64.0 >= key_bytes &&
+         n >= 2 * n_buckets(&idx->g);  // below two queries per bucket most tiles hold one query
+}
+
+IndexShape index_shape(const ksh_kss_index* idx) {
+  return IndexShape{idx->ctx, idx->g, idx->n_nodes, idx->words, idx->wt, idx->d_flags};
+}
+
+int index_lookup(ksh_kss_index* idx, bool join, const uint64_t* d_kmers, int64_t n, int canon, uint64_t* d_rows) {
+  return KSH_BY_KEY(idx->g.key_bytes, dispatch, idx, join, d_kmers, n, canon, d_rows);
+}
+
+void index_set_routes(ksh_kss_index* idx, uint32_t routes) { idx->routes = routes; }
+
 static void free_index(ksh_kss_index* x) {
   if (!x) return;
   if (x->ctx) {
@@ -497,20 +518,9 @@ int ksh_kss_index_query(ksh_kss_index* idx, const uint64_t* d_kmers, int64_t n, 
   ksh_ctx* ctx = idx->ctx;
   KSH_HIP(hipSetDevice(ctx->device));
   KSH_HIP(hipMemsetAsync(idx->d_flags, 0, 16, ctx->stream));
-  // auto: the join streams every touched slice once; the search costs each query about one 64-byte
-  // sector per node (the upper levels of its searches hit the cache).  Join once the search's sectors
-  // would outweigh one pass over the resident keys, and the batch fills the buckets: a join tile walks
-  // every node with two barriers whatever it holds, so at one query per tile the search is cheaper.
-  // Keys that fit the Infinity Cache serve the search's sectors from the cache: search.
-  bool join = route == 2;
-  if (route == 0) {
-    const double key_bytes = double(idx->total_keys) * idx->g.key_bytes;
-    join = key_bytes > double(kCacheBytes) && double(n) * idx->n_nodes * 64.0 >= key_bytes &&
-           n >= 2 * n_buckets(&idx->g);  // below two queries per bucket most tiles hold one query
-  }
-
+  const bool join = route == 2 || (route == 0 && index_auto_joins(idx, n));
   idx->routes = join ? KSH_QROUTE_JOIN : KSH_QROUTE_SEARCH;
-  return KSH_BY_KEY(idx->g.key_bytes, dispatch, idx, join, d_kmers, n, canonicalize ? 1 : 0, d_rows);
+  return index_lookup(idx, join, d_kmers, n, canonicalize ? 1 : 0, d_rows);
 }
 
 int ksh_kss_index_info(const ksh_kss_index* idx, int32_t* n_nodes, int32_t* words_per_row, int64_t* resident_bytes) {

@@ -184,6 +184,7 @@ def lib():
         "ksh_kss_index_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]),
         "ksh_kss_index_routes": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "ksh_kss_index_destroy": (C.c_int, [vp]),
+        "ksh_seq_hits": (C.c_int, [C.POINTER(SpssView), vp, C.c_int, C.c_int, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -988,14 +989,14 @@ class DeviceKmerSetSet:
             lib().ksh_free(dev, d_keys)
 
 
-QROUTE_SEARCH, QROUTE_JOIN, QROUTE_OVERSIZE, QROUTE_CHUNKED = 1, 2, 4, 8
+QROUTE_SEARCH, QROUTE_JOIN, QROUTE_OVERSIZE, QROUTE_CHUNKED, QROUTE_SEQ_PASSES = 1, 2, 4, 8, 16
 
 
 class KssIndex:
     """ksh_kss_index: which nodes' Get(i) hold each query k-mer (kmer_set_set.h:433-454), for every node i."""
 
-    def __init__(self, ctx, h, keep, borrowed=None):
-        self.ctx, self.h, self._keep, self._borrowed = ctx, h, keep, borrowed
+    def __init__(self, ctx, h, keep, borrowed=None, g=None):
+        self.ctx, self.h, self._keep, self._borrowed, self.g = ctx, h, keep, borrowed, g
         n, w, b = C.c_int32(), C.c_int32(), C.c_int64()
         check(lib().ksh_kss_index_info(h, C.byref(n), C.byref(w), C.byref(b)))
         self.n_nodes, self.words = n.value, w.value
@@ -1005,7 +1006,7 @@ class KssIndex:
         """Borrows the resident node sets of a built DeviceKmerSetSet (kept alive by the index)."""
         h = C.c_void_p()
         check(lib().ksh_kss_index_from_kss(dkss.h, C.byref(h)))
-        return cls(dkss.ctx, h, dkss, borrowed=dkss)
+        return cls(dkss.ctx, h, dkss, borrowed=dkss, g=dkss.g)
 
     def _handle(self):
         """The live index; an index whose borrowed structure was closed is closed too (its node sets are gone)."""
@@ -1031,7 +1032,7 @@ class KssIndex:
         check(lib().ksh_kss_index_create(ctx.h, C.byref(compacts[0].g if n else Geom()), views, n,
                                           offs.ctypes.data_as(C.POINTER(C.c_int64)),
                                           ids.ctypes.data_as(C.POINTER(C.c_int32)), int(canonical), C.byref(h)))
-        return cls(ctx, h, list(compacts))
+        return cls(ctx, h, list(compacts), g=compacts[0].g if n else None)
 
     def query(self, kmers, canonicalize=True, route=0, packed=False):
         """Rows for the 2K-bit patterns `kmers` (numpy, or a device torch tensor of int64/uint64): an n x n_nodes
@@ -1056,6 +1057,24 @@ class KssIndex:
         host = rows.cpu().numpy().view(np.uint64)
         bits = np.unpackbits(host.view(np.uint8).reshape(n, self.words * 8), axis=1, bitorder="little")
         return bits[:, : self.n_nodes].astype(bool)
+
+    def seq_hits(self, seqs, canonicalize=True, route=0, pass_positions=0, device=False):
+        """ksh_seq_hits: for every sequence of `seqs` (a DeviceSpss, or a list of str over ACGT, each at least K
+        long, uploaded through DeviceSpss.from_strings) and every node i, the number of the sequence's k-mer
+        positions whose k-mer is in Get(i): a uint32 array [n_seqs, n_nodes] (numpy; device=True: a torch.uint32
+        tensor that stays on the device)."""
+        import torch
+
+        h = self._handle()
+        if not isinstance(seqs, DeviceSpss):
+            seqs = DeviceSpss.from_strings(self.g, list(seqs), self.ctx.device)
+        n = seqs.n_strings
+        hits = torch.empty((max(n, 1), self.n_nodes), dtype=torch.int32, device=self.ctx.device)
+        view = seqs.view()
+        check(lib().ksh_seq_hits(C.byref(view), h, int(bool(canonicalize)), int(route), int(pass_positions),
+                                 hits.data_ptr()))
+        hits = hits[:n]
+        return hits.view(torch.uint32) if device else hits.cpu().numpy().view(np.uint32)
 
     def routes(self):
         bits = C.c_uint32()
