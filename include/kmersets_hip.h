@@ -167,8 +167,8 @@ int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
  * Every other call leaves every pending plan exact: hash, contains, kmers, diff, ksh_pair_weights,
  * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
  * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
- * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits and the accessors of a ksh_kss / ksh_kss_index, plans
- * and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
+ * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts and the accessors of a ksh_kss /
+ * ksh_kss_index, plans and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
  * plan: nothing else uses their slot.
  *
  * A failed plan ends the older plan of its group (it has overwritten the group's scratch) and leaves none: the
@@ -608,14 +608,17 @@ int ksh_kss_index_query(ksh_kss_index* idx, const uint64_t* d_kmers, int64_t n, 
 /* n_nodes, W, and the bytes of the resident sets the index reads (offsets included). */
 int ksh_kss_index_info(const ksh_kss_index* idx, int32_t* n_nodes, int32_t* words_per_row,
                        int64_t* resident_bytes);
-/* The routes the last query (ksh_kss_index_query or ksh_seq_hits) took, a mask of KSH_QROUTE_* (synchronises the
- * stream). */
+/* The routes the last query (ksh_kss_index_query, ksh_seq_hits or ksh_kss_pair_counts) took, a mask of KSH_QROUTE_*
+ * (synchronises the stream). */
 enum {
   KSH_QROUTE_SEARCH = 1 << 0,    /* per-query search                                            */
   KSH_QROUTE_JOIN = 1 << 1,      /* bucket join                                                  */
   KSH_QROUTE_OVERSIZE = 1 << 2,  /* ... some node's slice outgrew the LDS stage: searched in HBM */
   KSH_QROUTE_CHUNKED = 1 << 3,   /* ... the batch took more than one pass of 2^24 queries        */
-  KSH_QROUTE_SEQ_PASSES = 1 << 4 /* ksh_seq_hits: the batch took more than one pass of positions */
+  KSH_QROUTE_SEQ_PASSES = 1 << 4, /* ksh_seq_hits: the batch took more than one pass of positions */
+  KSH_QROUTE_PAIR_SPLIT = 1 << 5, /* ksh_kss_pair_counts: some bucket's k-mers did not fit one tile and were cut by
+                                     key range                                                    */
+  KSH_QROUTE_PAIR_FLUSH = 1 << 6  /* ... some workgroup flushed its counters before its last tile */
 };
 int ksh_kss_index_routes(const ksh_kss_index* idx, uint32_t* bits);
 int ksh_kss_index_destroy(ksh_kss_index* idx);
@@ -641,6 +644,35 @@ int ksh_kss_index_destroy(ksh_kss_index* idx);
  * of its ksh_kss and must not be used after ksh_kss_destroy. */
 int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int canonicalize, int route,
                  int64_t pass_positions, uint32_t* d_hits);
+
+/* ---- Pairwise intersection counts of the sets of a KmerSetSet ---------------------------------------
+ * d_counts[a * n_cols + b] = |Get(cols[a]) & Get(cols[b])| (kmer_set_set.h:433-454), exact, from one pass over the
+ * index's resident node sets: nothing is decompressed and no Get(i) is formed.  The matrix is symmetric and its
+ * diagonal is |Get(cols[a])|; the exact Jaccard similarity of two sets is c_ab / (c_aa + c_bb - c_ab).
+ * cols: HOST array of n_cols distinct node ids in any order, 1 <= n_cols <= 128 (the inputs are ids
+ * 0 .. n_inputs - 1; internal nodes are allowed).  It is only read during the call.  NULL: all nodes in order
+ * (n_cols is ignored), refused on an index of more than 128 nodes.  A larger collection is covered by several
+ * calls: cut the ids into blocks of at most 64, and call once per pair of blocks with cols = the two blocks one
+ * after the other (and once per block alone, or with any partner, for its diagonal block); the off-diagonal
+ * quadrant of each result is the block pair's part of the table.
+ * d_counts: device int64[n_cols * n_cols], written in full, zeros included.
+ * n_distinct (host, may be NULL): the number of distinct k-mers held by any node of the index -- all nodes, not only
+ * cols.  When it is non-NULL the call synchronises the stream once; otherwise the work is only enqueued on the
+ * index's context stream.
+ * flush_rows: the rows (distinct k-mers with their column bits) a workgroup accumulates in its 32-bit on-chip
+ * counters between flushes to d_counts.  0: the default, 2^31 - 2048 -- a counter grows by at most one per row and
+ * a workgroup checks after every tile of at most 1024 rows, so no counter can reach 2^31.  Any value >= 1 is taken
+ * as it is (values above the default as the default); small values only make the pass slower.
+ * ksh_kss_index_routes reports KSH_QROUTE_PAIR_SPLIT and KSH_QROUTE_PAIR_FLUSH for the last call.
+ * The pass reads every node's offsets of every bucket: at large N (2^20 buckets and more) that, not the keys, is
+ * most of what it reads -- correct, and slow.
+ * KSH_INVALID_ARGUMENT, each with a message and before any device work: NULL idx or d_counts, n_cols outside
+ * [1, 128] with non-NULL cols, an id outside [0, n_nodes), a repeated id, a negative flush_rows, NULL cols on an
+ * index of more than 128 nodes.
+ * Scratch comes from the context's pool and is given back before the call returns; the call keeps nothing and
+ * ends no pending plan.  (As in ksh_seq_hits, the index is not the first parameter: the columns asked for are.)  The index must be usable as for ksh_kss_index_query. */
+int ksh_kss_pair_counts(const int32_t* cols, int32_t n_cols, ksh_kss_index* idx, int64_t flush_rows,
+                        int64_t* d_counts, int64_t* n_distinct);
 
 #ifdef __cplusplus
 }

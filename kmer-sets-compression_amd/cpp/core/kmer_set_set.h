@@ -324,6 +324,19 @@ class KmerSetSetIndex {
     return CountHits(KmerSetCompact<K, N, KeyType>::FromStrings(sequences), canonical);
   }
 
+  // Exact pairwise intersection counts (ksh_kss_pair_counts): element a * n + b is |Get(cols[a]) & Get(cols[b])|,
+  // n = cols.size(); at most 128 distinct node ids in any order.  Empty `cols`: all nodes in order (n = Nodes(),
+  // refused above 128 nodes).
+  std::vector<std::int64_t> PairCounts(const std::vector<int>& cols = {}) const {
+    const std::vector<std::int32_t> ids(cols.begin(), cols.end());
+    const std::size_t n = ids.empty() ? std::size_t(nodes_) : ids.size();
+    const std::size_t side = n < 128 ? n : 128;  // (what the call refuses is never written)
+    ksc::DeviceBuffer d_counts(side * side * 8);
+    ksc::Check(ksh_kss_pair_counts(ids.empty() ? nullptr : ids.data(), static_cast<std::int32_t>(ids.size()), index_,
+                                   0, static_cast<std::int64_t*>(d_counts.get()), nullptr));
+    return d_counts.ToHost<std::int64_t>(n * n);
+  }
+
  private:
   ksh_kss_index* index_ = nullptr;
   std::int32_t words_ = 0, nodes_ = 0;

@@ -201,14 +201,25 @@ void cover_launch_emit(hipStream_t st, const ksh_spss_view* in, const int64_t* i
 // The context and geometry a KmerSetSet was built on (ksh_kss.hip; the query index borrows both).
 int kss_context(const ksh_kss* k, ksh_ctx** ctx, ksh_geom* g);
 
-// What ksh_seq_hits (ksh_seqhits.hip) needs of a query index (ksh_query.hip): its shape, the auto rule of
+// What ksh_seq_hits (ksh_seqhits.hip) and ksh_kss_pair_counts (ksh_paircounts.hip) need of a query index (ksh_query.hip): its shape, the auto rule of
 // ksh_kss_index_query for a batch of n, one look-up of n patterns on the search or the join route (rows in the
 // patterns' order; it leaves the index's route bits alone), and the route bits ksh_kss_index_routes reports.
+// One node's resident set, as the index's kernels read it.
+struct NodeRef {
+  const int64_t* off;  // int64[2^N + 1]
+  const void* keys;
+  int64_t n;
+};
+// d_flags: int[4] -- [0] the join searched an oversize slice in global memory, [1] ksh_kss_pair_counts cut a bucket
+// by key range, [2] one of its workgroups flushed its counters before its last tile.
 struct IndexShape {
   ksh_ctx* ctx;
   ksh_geom g;
   int32_t n_nodes, words, wt;  // wt: words padded to a power of two (the look-up kernels' template width)
   int* d_flags;
+  const NodeRef* d_nodes;      // n_nodes of them; what ksh_kss_pair_counts (ksh_paircounts.hip) walks
+  const uint64_t* d_anc;       // n_nodes * wt words
+  int64_t total_keys;          // keys of all nodes together
 };
 IndexShape index_shape(const ksh_kss_index* idx);
 bool index_auto_joins(const ksh_kss_index* idx, int64_t n);

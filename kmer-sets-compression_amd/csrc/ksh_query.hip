@@ -18,11 +18,7 @@
 
 namespace {
 
-struct NodeRef {
-  const int64_t* off;  // int64[2^N + 1]
-  const void* keys;
-  int64_t n;
-};
+using ksh::NodeRef;
 
 constexpr int kMaxWords = 16;                  // rows up to 1024 nodes, in registers / LDS
 constexpr int64_t kChunk = int64_t(1) << 24;   // join: queries per pass (bounds the scratch)
@@ -52,7 +48,7 @@ struct ksh_kss_index {
   int64_t total_keys = 0, resident_bytes = 0;
   NodeRef* d_nodes = nullptr;   // pooled
   uint64_t* d_anc = nullptr;    // n_nodes * wt words, pooled
-  int* d_flags = nullptr;       // [0]: the join searched an oversize slice in global memory
+  int* d_flags = nullptr;       // int[4], see IndexShape
   std::vector<void*> owned;     // from nodes: the decoded sets (pooled)
   uint32_t routes = 0;
 };
@@ -318,7 +314,8 @@ bool index_auto_joins(const ksh_kss_index* idx, int64_t n) {
 }
 
 IndexShape index_shape(const ksh_kss_index* idx) {
-  return IndexShape{idx->ctx, idx->g, idx->n_nodes, idx->words, idx->wt, idx->d_flags};
+  return IndexShape{idx->ctx, idx->g,        idx->n_nodes, idx->words,     idx->wt,
+                    idx->d_flags, idx->d_nodes, idx->d_anc,  idx->total_keys};
 }
 
 int index_lookup(ksh_kss_index* idx, bool join, const uint64_t* d_kmers, int64_t n, int canon, uint64_t* d_rows) {
@@ -535,9 +532,11 @@ int ksh_kss_index_routes(const ksh_kss_index* idx, uint32_t* bits) {
   if (!idx || !bits) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
   ksh_ctx* ctx = idx->ctx;
   KSH_HIP(hipSetDevice(ctx->device));
-  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, idx->d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
+  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, idx->d_flags, 12, hipMemcpyDeviceToHost, ctx->stream));
   KSH_HIP(hipStreamSynchronize(ctx->stream));
-  *bits = idx->routes | (*reinterpret_cast<const int*>(ctx->h_pinned) ? uint32_t(KSH_QROUTE_OVERSIZE) : 0u);
+  const int* flags = reinterpret_cast<const int*>(ctx->h_pinned);
+  *bits = idx->routes | (flags[0] ? uint32_t(KSH_QROUTE_OVERSIZE) : 0u) |
+          (flags[1] ? uint32_t(KSH_QROUTE_PAIR_SPLIT) : 0u) | (flags[2] ? uint32_t(KSH_QROUTE_PAIR_FLUSH) : 0u);
   return KSH_OK;
 }
 

@@ -185,6 +185,7 @@ def lib():
         "ksh_kss_index_routes": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "ksh_kss_index_destroy": (C.c_int, [vp]),
         "ksh_seq_hits": (C.c_int, [C.POINTER(SpssView), vp, C.c_int, C.c_int, i64, vp]),
+        "ksh_kss_pair_counts": (C.c_int, [C.POINTER(i32), i32, vp, i64, vp, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -990,6 +991,7 @@ class DeviceKmerSetSet:
 
 
 QROUTE_SEARCH, QROUTE_JOIN, QROUTE_OVERSIZE, QROUTE_CHUNKED, QROUTE_SEQ_PASSES = 1, 2, 4, 8, 16
+QROUTE_PAIR_SPLIT, QROUTE_PAIR_FLUSH = 32, 64
 
 
 class KssIndex:
@@ -1075,6 +1077,37 @@ class KssIndex:
                                  hits.data_ptr()))
         hits = hits[:n]
         return hits.view(torch.uint32) if device else hits.cpu().numpy().view(np.uint32)
+
+    def pair_counts(self, cols=None, flush_rows=0, device=False, with_distinct=False):
+        """ksh_kss_pair_counts: counts[a, b] = |Get(cols[a]) & Get(cols[b])|, exact, as an int64 array
+        [n_cols, n_cols] (numpy; device=True: a torch tensor that stays on the device).  cols: up to 128 distinct
+        node ids in any order; None: all nodes in order (an index of more than 128 nodes is refused: name the
+        columns, two blocks of at most 64 per call).  with_distinct=True returns (counts, the number of distinct
+        k-mers held by any node of the index)."""
+        import torch
+
+        h = self._handle()
+        if cols is None:
+            n, ids = self.n_nodes, None
+        else:
+            arr = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+            n = int(arr.size)
+            ids = (arr if n else np.zeros(1, dtype=np.int32)).ctypes.data_as(C.POINTER(C.c_int32))  # (never NULL)
+        side = min(max(n, 1), 128)  # (what the call refuses is never written)
+        counts = torch.empty((side, side), dtype=torch.int64, device=self.ctx.device)
+        distinct = C.c_int64()
+        check(lib().ksh_kss_pair_counts(ids, n, h, int(flush_rows), counts.data_ptr(),
+                                        C.byref(distinct) if with_distinct else None))
+        out = counts if device else counts.cpu().numpy()
+        return (out, distinct.value) if with_distinct else out
+
+    def jaccard(self, cols=None):
+        """Exact Jaccard similarities c_ab / (c_aa + c_bb - c_ab) of the sets Get(cols[a]), a float64 numpy array
+        computed on the host from pair_counts(cols).  Two empty sets (0 / 0) are defined as 1.0."""
+        c = self.pair_counts(cols).astype(np.float64)
+        d = np.diag(c)
+        union = d[:, None] + d[None, :] - c
+        return np.where(union > 0, c / np.where(union > 0, union, 1.0), 1.0)
 
     def routes(self):
         bits = C.c_uint32()
