@@ -448,7 +448,15 @@ int ksh_spss_cover_release(ksh_ctx* ctx);
  * must stay alive while they are nodes of the result, and the context must outlive the
  * result.  The three re-encodes of a merge (:345-360) are deferred to the points where the
  * reference reads them (Weight() at the convergence checks, :287, and the final nodes): same
- * values, fewer encodes.  Synchronises the stream before returning. */
+ * values, fewer encodes.  Synchronises the stream before returning.
+ * n_inputs == 0 (inputs, and in ksh_kss_build_owned owners, may then be NULL; so may bucket_ids when
+ * n_ids == 0) is no error on any of the three entry points: KSH_OK and a structure of 0 nodes, as the
+ * reference's constructor leaves one (no weights, the loop breaks at once).  Nothing is launched and, in the
+ * multi-rank builds, nothing is exchanged -- n_inputs is the same on every rank.  Its accessors work:
+ * ksh_kss_size 0, ksh_kss_trace 0 iterations and 0 checkpoints, ksh_kss_initial_weights 0 entries,
+ * ksh_kss_stats all 0, ksh_kss_meta "0" (an empty adjacency list), ksh_kss_children none; ksh_kss_node,
+ * ksh_kss_node_holder and ksh_kss_get answer KSH_INVALID_ARGUMENT for every i (there is no node i).
+ * A negative n_inputs or n_ids, and a NULL array with a positive count, are KSH_INVALID_ARGUMENT. */
 typedef struct ksh_kss ksh_kss;
 int ksh_kss_build(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* inputs, int32_t n_inputs,
                   const int32_t* bucket_ids, int32_t n_ids, int canonical, int32_t max_iterations,

@@ -1639,6 +1639,7 @@ static int build_single(ksh_kss* k, const ksh_spss_view* inputs, int32_t n_input
   };
   std::vector<Step> seq;
   bool seq_complete = false;  // the control loop itself has ended (no common k-mers left / max_iterations)
+  bool seq_ran_dry = false;   // ... on weight == 0, which the reference finds out AFTER the check of that iteration
   std::map<std::pair<int, int>, int64_t> weights;
   {
     PhaseTimer pt(k, 1);
@@ -1684,7 +1685,7 @@ static int build_single(ksh_kss* k, const ksh_spss_view* inputs, int32_t n_input
           weight = p.second;
         }
       if (weight == 0) {
-        seq_complete = true;
+        seq_complete = seq_ran_dry = true;
         break;
       }
       seq.push_back({j, kk, weight});
@@ -1755,7 +1756,10 @@ static int build_single(ksh_kss* k, const ksh_spss_view* inputs, int32_t n_input
   int done = 0;  // iterations run
   for (int i = 0;; i++) {
     KSH_TRY(extend_sequence(i + 2 * interval));
-    if (i >= int(seq.size())) break;  // the control loop ended here
+    // the control loop ended here: at max_iterations before the check of this iteration, on weight == 0 after it
+    // (kmer_set_set.h: the check comes between the two breaks)
+    const bool ended = i >= int(seq.size());
+    if (ended && !seq_ran_dry) break;
     if (i > 0 && i % interval == 0) {
       int64_t updated = 0;
       KSH_TRY(total_spss_weight_now(i, &updated));
@@ -1766,6 +1770,7 @@ static int build_single(ksh_kss* k, const ksh_spss_view* inputs, int32_t n_input
       if (stop) break;
       total_spss_weight = updated;
     }
+    if (ended) break;
     const int n = int(k->compacts.size());
     const int j = seq[size_t(i)].j, kk = seq[size_t(i)].kk;
     const int64_t original_size = k->compacts[size_t(j)].size + k->compacts[size_t(kk)].size;
@@ -1849,7 +1854,7 @@ extern "C" {
 int ksh_kss_build(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* inputs, int32_t n_inputs,
                   const int32_t* bucket_ids, int32_t n_ids, int canonical_flag,
                   int32_t max_iterations, ksh_kss** out) {
-  if (!ctx || !out || (n_inputs > 0 && !inputs)) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
+  if (!ctx || !out || (n_inputs > 0 && !inputs) || (n_ids > 0 && !bucket_ids)) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
   *out = nullptr;
   KSH_TRY(check_geom(g));
   if (n_inputs < 0 || n_ids < 0) return fail(KSH_INVALID_ARGUMENT, "negative count");
@@ -1861,7 +1866,8 @@ int ksh_kss_build(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* inputs, 
   k->ctx = ctx;
   k->g = *g;
   k->canonical = canonical_flag;
-  std::vector<int32_t> ids(bucket_ids, bucket_ids + n_ids);
+  std::vector<int32_t> ids;
+  if (n_ids > 0) ids.assign(bucket_ids, bucket_ids + n_ids);
   // KSH_KSS_LOOP=ahead: the control loop run on the samples ahead of the sets, so that stale nodes the
   // loop merges again are only weighed (build_single).  Measured on 64 x 10^8 (7 checks): it skips the
   // write of 45 % of the encoded k-mers, and gives the time back when the last check stops the loop and
@@ -1871,6 +1877,7 @@ int ksh_kss_build(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* inputs, 
     return e && std::string(e) == "ahead";
   }();
   int rc = KSH_OK;
+  k->meta = serialize_children(k->children);  // (no inputs: a structure of 0 nodes, "0" as the reference writes an empty DAG)
   if (n_inputs > 0)
     rc = control_ahead ? build_single(k, inputs, n_inputs, ids, max_iterations) : build(k, inputs, n_inputs, ids, max_iterations);
   if (rc != KSH_OK) {
@@ -1885,7 +1892,7 @@ int ksh_kss_build_sharded(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* 
                           const int32_t* bucket_ids, int32_t n_ids, int canonical_flag,
                           int32_t max_iterations, int32_t rank, int32_t world, ksh_allgather_i64 gather,
                           void* gather_user, ksh_kss** out) {
-  if (!ctx || !out || (n_inputs > 0 && !inputs)) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
+  if (!ctx || !out || (n_inputs > 0 && !inputs) || (n_ids > 0 && !bucket_ids)) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
   *out = nullptr;
   KSH_TRY(check_geom(g));
   if (n_inputs < 0 || n_ids < 0) return fail(KSH_INVALID_ARGUMENT, "negative count");
@@ -1903,8 +1910,10 @@ int ksh_kss_build_sharded(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* 
   k->world = world;
   k->gather = gather;
   k->gather_user = gather_user;
-  std::vector<int32_t> ids(bucket_ids, bucket_ids + n_ids);
+  std::vector<int32_t> ids;
+  if (n_ids > 0) ids.assign(bucket_ids, bucket_ids + n_ids);
   int rc = KSH_OK;
+  k->meta = serialize_children(k->children);  // (no inputs: 0 nodes, no exchange)
   if (n_inputs > 0) rc = build(k, inputs, n_inputs, ids, max_iterations);
   if (rc != KSH_OK) {
     ksh_kss_destroy(k);
@@ -1917,7 +1926,8 @@ int ksh_kss_build_sharded(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* 
 int ksh_kss_build_owned(ksh_ctx* ctx, ksh_comm* comm, const ksh_geom* g, const ksh_spss_view* inputs,
                         int32_t n_inputs, const int32_t* owners, const int32_t* bucket_ids, int32_t n_ids,
                         int canonical_flag, int32_t max_iterations, ksh_kss** out) {
-  if (!ctx || !comm || !out || (n_inputs > 0 && (!inputs || !owners))) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
+  if (!ctx || !comm || !out || (n_inputs > 0 && (!inputs || !owners)) || (n_ids > 0 && !bucket_ids))
+    return fail(KSH_INVALID_ARGUMENT, "NULL argument");
   *out = nullptr;
   KSH_TRY(check_geom(g));
   if (n_inputs < 0 || n_ids < 0) return fail(KSH_INVALID_ARGUMENT, "negative count");
@@ -1935,8 +1945,10 @@ int ksh_kss_build_owned(ksh_ctx* ctx, ksh_comm* comm, const ksh_geom* g, const k
   k->rank = comm_rank(comm);
   k->world = world;
   k->comm = comm;
-  std::vector<int32_t> ids(bucket_ids, bucket_ids + n_ids);
+  std::vector<int32_t> ids;
+  if (n_ids > 0) ids.assign(bucket_ids, bucket_ids + n_ids);
   int rc = KSH_OK;
+  k->meta = serialize_children(k->children);  // (no inputs: 0 nodes on every rank, nothing is exchanged)
   if (n_inputs > 0) rc = build_owned(k, inputs, n_inputs, owners, ids, max_iterations);
   ctx->inject_skip = -1;
   if (rc != KSH_OK) {

@@ -827,12 +827,13 @@ class DeviceKmerSetSet:
     """ksh_kss: KmerSetSet built on device (lib/core/kmer_set_set.h:109-427)."""
 
     def __init__(self, ctx, compacts, bucket_ids, canonical=True, max_iterations=-1, dist=None,
-                 dist_device="cpu"):
+                 dist_device="cpu", g=None):
         """dist: an initialised torch.distributed module (one process per GPU) for the sharded
         build (ksh_kss_build_sharded): every rank passes the same inputs; the SPSS of a node
-        lives on one rank (node_holder)."""
-        self.ctx, self.g, self.inputs = ctx, compacts[0].g, list(compacts)
-        views = (SpssView * len(compacts))(*[c.view() for c in compacts])
+        lives on one rank (node_holder).  g: the geometry, needed only where there is no input to
+        take it from (no inputs at all: a structure of 0 nodes)."""
+        self.ctx, self.g, self.inputs = ctx, g if g is not None else compacts[0].g, list(compacts)
+        views = (SpssView * max(len(compacts), 1))(*[c.view() for c in compacts])
         ids = np.ascontiguousarray(bucket_ids, dtype=np.int32)
         h = C.c_void_p()
         if dist is None:
@@ -1041,6 +1042,12 @@ class KssIndex:
         bool array, or with packed=True the n x W uint64 rows (a device tensor stays on the device)."""
         import torch
 
+        with torch.cuda.stream(self.ctx.stream):   # (another context made since may have become torch's current stream)
+            return self._query(kmers, canonicalize, route, packed)
+
+    def _query(self, kmers, canonicalize, route, packed):
+        import torch
+
         on_device = isinstance(kmers, torch.Tensor)
         if on_device:
             q = kmers.contiguous()
@@ -1067,6 +1074,12 @@ class KssIndex:
         tensor that stays on the device)."""
         import torch
 
+        with torch.cuda.stream(self.ctx.stream):
+            return self._seq_hits(seqs, canonicalize, route, pass_positions, device)
+
+    def _seq_hits(self, seqs, canonicalize, route, pass_positions, device):
+        import torch
+
         h = self._handle()
         if not isinstance(seqs, DeviceSpss):
             seqs = DeviceSpss.from_strings(self.g, list(seqs), self.ctx.device)
@@ -1084,6 +1097,12 @@ class KssIndex:
         node ids in any order; None: all nodes in order (an index of more than 128 nodes is refused: name the
         columns, two blocks of at most 64 per call).  with_distinct=True returns (counts, the number of distinct
         k-mers held by any node of the index)."""
+        import torch
+
+        with torch.cuda.stream(self.ctx.stream):
+            return self._pair_counts(cols, flush_rows, device, with_distinct)
+
+    def _pair_counts(self, cols, flush_rows, device, with_distinct):
         import torch
 
         h = self._handle()
@@ -1230,18 +1249,20 @@ class OwnedKmerSetSet(DeviceKmerSetSet):
     compacts[i] is the input's DeviceSpss on its owner and None elsewhere."""
 
     def __init__(self, ctx, compacts, bucket_ids, dist, coll_dev, canonical=True, max_iterations=-1, owners=None,
-                 comm=None):
+                 comm=None, g=None):
+        """g: the geometry, for a rank that owns no input to take it from (fewer inputs than ranks)."""
         self.ctx, self.dist, self.coll_dev = ctx, dist, coll_dev
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         self.owners = list(owners) if owners is not None else block_owners(len(compacts), self.world)
         mine = [c for c in compacts if c is not None]
-        if not mine:
-            raise ValueError("rank %d owns no input" % self.rank)
-        self.g, self.inputs = mine[0].g, list(compacts)
+        if not mine and g is None:
+            raise ValueError("rank %d owns no input: pass the geometry (g=)" % self.rank)
+        self.g, self.inputs = g if g is not None else mine[0].g, list(compacts)
         for i, c in enumerate(compacts):
             if (c is not None) != (self.owners[i] == self.rank):
                 raise ValueError("input %d: the container must be given on its owner (rank %d) only" % (i, self.owners[i]))
-        views = (SpssView * len(compacts))(*[c.view() if c is not None else SpssView(None, None, 0, 0) for c in compacts])
+        views = (SpssView * max(len(compacts), 1))(*[c.view() if c is not None else SpssView(None, None, 0, 0)
+                                                     for c in compacts])
         own = np.ascontiguousarray(self.owners, dtype=np.int32)
         ids = np.ascontiguousarray(bucket_ids, dtype=np.int32)
         self._own_comm = comm is None

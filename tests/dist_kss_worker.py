@@ -1,7 +1,12 @@
 """Worker of tests/test_gpu_kmer_set_set.py::test_sharded_build: one of N ranks (all on GPU 0, gloo
 for the exchange) building the same KmerSetSet with ksh_kss_build_sharded.  Every rank checks
 the replicated state against the oracle; the SPSS strings are checked by the rank that holds
-them, and every node must be held by exactly the rank the deal says."""
+them, and every node must be held by exactly the rank the deal says.
+
+  ... dist_kss_worker.py K N KEY_BYTES N_SETS SIZE SEED [family=NAME]
+
+family=NAME (last): the sets, the geometry and the bucket ids of that family of tests/loop_families.py instead of
+phylogeny_sets(K, N_SETS, SIZE, SEED); the six numbers are then read and ignored."""
 import json
 import os
 import sys
@@ -18,16 +23,24 @@ from kmersets import capi, synth  # noqa: E402
 
 
 def main():
-    k, n, kb, n_sets, size, seed = (int(x) for x in sys.argv[1:7])
+    argv = list(sys.argv)
+    fam = argv.pop()[len("family="):] if argv[-1].startswith("family=") else None
+    k, n, kb, n_sets, size, seed = (int(x) for x in argv[1:7])
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     dist.init_process_group("gloo")
     rank, world = dist.get_rank(), dist.get_world_size()
     torch.cuda.set_device(0)
     ctx = capi.Context(0)
-    sets = synth.phylogeny_sets(k, n_sets, size, seed=seed)
+    if fam is not None:
+        import loop_families
+
+        k, n, kb, sets, ids = loop_families.family(fam)
+        n_sets = len(sets)
+    else:
+        sets = synth.phylogeny_sets(k, n_sets, size, seed=seed)
+        ids = synth.sample_bucket_ids(n, seed=seed + 1)
     osets = [ol.Set.from_kmers(k, n, kb, s) for s in sets]
     ocompacts = [s.compact() for s in osets]
-    ids = synth.sample_bucket_ids(n, seed=seed + 1)
     okss = ol.KmerSetSet(ocompacts, ids)
     g = capi.geom(k, n)
     dcompacts = [capi.DeviceSpss.from_strings(g, c.strings(), ctx.device) for c in ocompacts]

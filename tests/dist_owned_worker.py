@@ -4,7 +4,12 @@ one KmerSetSet with ksh_kss_build_owned.  KSH_OWNED_BACKEND=nccl (::test_owned_b
 box with two GPUs or more): one GPU per rank and the library's own RCCL transport on device buffers --
 ncclSend / ncclRecv pairs, the side communicator, the deferred all-gathers.  Every input is decoded by its owner only; every rank
 checks the replicated state (trace, checkpoints, DAG, sizes) against the oracle, and the rank that
-owns a node checks its set and its SPSS strings; nobody else can read them."""
+owns a node checks its set and its SPSS strings; nobody else can read them.
+
+  ... dist_owned_worker.py K N KEY_BYTES N_SETS SIZE SEED [block|striped] [family=NAME]
+
+family=NAME (last): the sets, the geometry and the bucket ids of that family of tests/loop_families.py instead of
+phylogeny_sets(K, N_SETS, SIZE, SEED); the six numbers are then read and ignored."""
 import json
 import os
 import sys
@@ -21,8 +26,10 @@ from kmersets import capi, synth  # noqa: E402
 
 
 def main():
-    k, n, kb, n_sets, size, seed = (int(x) for x in sys.argv[1:7])
-    layout = sys.argv[7] if len(sys.argv) > 7 else "block"
+    argv = list(sys.argv)
+    fam = argv.pop()[len("family="):] if argv[-1].startswith("family=") else None
+    k, n, kb, n_sets, size, seed = (int(x) for x in argv[1:7])
+    layout = argv[7] if len(argv) > 7 else "block"
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     backend = os.environ.get("KSH_OWNED_BACKEND", "gloo")
     if backend == "nccl":
@@ -37,10 +44,16 @@ def main():
         coll_dev = "cpu"
     rank, world = dist.get_rank(), dist.get_world_size()
     ctx = capi.Context(local)
-    sets = synth.phylogeny_sets(k, n_sets, size, seed=seed)
+    if fam is not None:
+        import loop_families
+
+        k, n, kb, sets, ids = loop_families.family(fam)
+        n_sets = len(sets)
+    else:
+        sets = synth.phylogeny_sets(k, n_sets, size, seed=seed)
+        ids = synth.sample_bucket_ids(n, seed=seed + 1)
     osets = [ol.Set.from_kmers(k, n, kb, s) for s in sets]
     ocompacts = [s.compact() for s in osets]
-    ids = synth.sample_bucket_ids(n, seed=seed + 1)
     okss = ol.KmerSetSet(ocompacts, ids)
     g = capi.geom(k, n)
     # "block": neighbours share a rank (most merges are local); "striped": siblings live on
@@ -48,7 +61,7 @@ def main():
     owners = capi.block_owners(n_sets, world) if layout == "block" else [i % world for i in range(n_sets)]
     dcompacts = [capi.DeviceSpss.from_strings(g, c.strings(), ctx.device) if owners[i] == rank else None
                  for i, c in enumerate(ocompacts)]
-    dkss = capi.OwnedKmerSetSet(ctx, dcompacts, ids, dist, coll_dev, owners=owners)
+    dkss = capi.OwnedKmerSetSet(ctx, dcompacts, ids, dist, coll_dev, owners=owners, g=g)
     transport = dkss.comm.kind
     ranks_seen = dkss.comm.ranks_seen()
     assert ranks_seen == world, (ranks_seen, world)

@@ -8,11 +8,15 @@ all-gather through a barrier, send / recv through one queue per (source, destina
 are those of tests/dist_owned_worker.py: the replicated state against the oracle on every rank, a
 node's set and SPSS on the rank that owns it.
 
-  python owned_threads_worker.py K N KEY_BYTES N_SETS SIZE SEED WORLD [block|striped] [expect_fail]
+  python owned_threads_worker.py K N KEY_BYTES N_SETS SIZE SEED WORLD [block|striped] [expect_fail] [family=NAME]
 
 expect_fail (with KSH_FAIL_INJECT=rank:skip:min_bytes in the environment: that rank's large allocations start
 failing): every rank's ksh_kss_build_owned must return an error -- the failed rank its own, the others "rank r
 failed" -- and none may be left waiting in an exchange.
+
+family=NAME (last): the sets, the geometry and the bucket ids of that family of tests/loop_families.py instead of
+phylogeny_sets(K, N_SETS, SIZE, SEED) -- K N KEY_BYTES N_SETS SIZE SEED are then read and ignored.  With fewer
+inputs than ranks some ranks own nothing.
 """
 import json
 import os
@@ -92,12 +96,12 @@ def run_rank(rank, hub, shape, layout, shared, out, errors, expect_fail=False):
                      for i, c in enumerate(ocompacts)]
         if expect_fail:
             try:
-                capi.OwnedKmerSetSet(ctx, dcompacts, ids, dist, "cpu", owners=owners)
+                capi.OwnedKmerSetSet(ctx, dcompacts, ids, dist, "cpu", owners=owners, g=g)
                 out[rank] = {"raised": False, "message": ""}
             except capi.KshError as e:
                 out[rank] = {"raised": True, "message": str(e)}
             return
-        dkss = capi.OwnedKmerSetSet(ctx, dcompacts, ids, dist, "cpu", owners=owners)
+        dkss = capi.OwnedKmerSetSet(ctx, dcompacts, ids, dist, "cpu", owners=owners, g=g)
         it, cp, imp = dkss.trace()
         assert np.array_equal(it, okss.iterations()), (it, okss.iterations())
         ocp, oimp = okss.checkpoints()
@@ -133,13 +137,21 @@ def run_rank(rank, hub, shape, layout, shared, out, errors, expect_fail=False):
 
 
 def main():
-    k, n, kb, n_sets, size, seed, world = (int(x) for x in sys.argv[1:8])
-    layout = sys.argv[8] if len(sys.argv) > 8 else "block"
-    expect_fail = len(sys.argv) > 9 and sys.argv[9] == "expect_fail"
-    sets = synth.phylogeny_sets(k, n_sets, size, seed=seed)
+    argv = list(sys.argv)
+    fam = argv.pop()[len("family="):] if argv[-1].startswith("family=") else None
+    k, n, kb, n_sets, size, seed, world = (int(x) for x in argv[1:8])
+    layout = argv[8] if len(argv) > 8 else "block"
+    expect_fail = len(argv) > 9 and argv[9] == "expect_fail"
+    if fam is not None:
+        import loop_families
+
+        k, n, kb, sets, ids = loop_families.family(fam)
+        n_sets = len(sets)
+    else:
+        sets = synth.phylogeny_sets(k, n_sets, size, seed=seed)
+        ids = synth.sample_bucket_ids(n, seed=seed + 1)
     osets = [ol.Set.from_kmers(k, n, kb, s) for s in sets]
     ocompacts = [s.compact() for s in osets]
-    ids = synth.sample_bucket_ids(n, seed=seed + 1)
     okss = ol.KmerSetSet(ocompacts, ids)
     shared = {"ocompacts": ocompacts, "okss": okss, "osets": osets, "ids": ids,
               "node_sizes": [okss.node(i).size() for i in range(okss.size())],
