@@ -167,7 +167,8 @@ int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
  * Every other call leaves every pending plan exact: hash, contains, kmers, diff, ksh_pair_weights,
  * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
  * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
- * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts and the accessors of a ksh_kss /
+ * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
+ * ksh_kss_select_keys and the accessors of a ksh_kss /
  * ksh_kss_index, plans and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
  * plan: nothing else uses their slot.
  *
@@ -616,16 +617,16 @@ int ksh_kss_index_query(ksh_kss_index* idx, const uint64_t* d_kmers, int64_t n, 
 /* n_nodes, W, and the bytes of the resident sets the index reads (offsets included). */
 int ksh_kss_index_info(const ksh_kss_index* idx, int32_t* n_nodes, int32_t* words_per_row,
                        int64_t* resident_bytes);
-/* The routes the last query (ksh_kss_index_query, ksh_seq_hits or ksh_kss_pair_counts) took, a mask of KSH_QROUTE_*
- * (synchronises the stream). */
+/* The routes the last query (ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count or
+ * ksh_kss_select_keys) took, a mask of KSH_QROUTE_* (synchronises the stream). */
 enum {
   KSH_QROUTE_SEARCH = 1 << 0,    /* per-query search                                            */
   KSH_QROUTE_JOIN = 1 << 1,      /* bucket join                                                  */
   KSH_QROUTE_OVERSIZE = 1 << 2,  /* ... some node's slice outgrew the LDS stage: searched in HBM */
   KSH_QROUTE_CHUNKED = 1 << 3,   /* ... the batch took more than one pass of 2^24 queries        */
   KSH_QROUTE_SEQ_PASSES = 1 << 4, /* ksh_seq_hits: the batch took more than one pass of positions */
-  KSH_QROUTE_PAIR_SPLIT = 1 << 5, /* ksh_kss_pair_counts: some bucket's k-mers did not fit one tile and were cut by
-                                     key range                                                    */
+  KSH_QROUTE_PAIR_SPLIT = 1 << 5, /* ksh_kss_pair_counts, ksh_kss_select_count, ksh_kss_select_keys: some bucket's
+                                     k-mers did not fit one tile and were cut by key range        */
   KSH_QROUTE_PAIR_FLUSH = 1 << 6  /* ... some workgroup flushed its counters before its last tile */
 };
 int ksh_kss_index_routes(const ksh_kss_index* idx, uint32_t* bits);
@@ -681,6 +682,61 @@ int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int canonicalize
  * ends no pending plan.  (As in ksh_seq_hits, the index is not the first parameter: the columns asked for are.)  The index must be usable as for ksh_kss_index_query. */
 int ksh_kss_pair_counts(const int32_t* cols, int32_t n_cols, ksh_kss_index* idx, int64_t flush_rows,
                         int64_t* d_counts, int64_t* n_distinct);
+
+/* ---- Selections: the k-mers that chosen sets of a KmerSetSet share, or do not -------------------------------
+ * For a k-mer q held by any node of the index, c(q) = the number of a with q in Get(cols[a]).  q is selected iff
+ *     min_count <= c(q) <= max_count,   q in Get(r) for every r of require,   q not in Get(x) for every x of exclude.
+ * min_count >= 1, so a selected k-mer always lies in the union of the columns.  Some selections over n columns:
+ * the union 1..n; the core n..n; private to s: require = {s}, max_count = 1; accessory 2..n-1; A & B \ C:
+ * cols = {A, B, C}, require = {A, B}, exclude = {C}.
+ * Both calls are stateless: each is one pass over the index's resident node sets (the pass of ksh_kss_pair_counts
+ * with another consumer: nothing is decompressed and no Get(i) is formed), they keep no plan in the context, join no
+ * plan group and end no pending plan -- which is why the second is not named *_write: that ending belongs to the
+ * two-call pairs of "Plans".  As in ksh_seq_hits and ksh_kss_pair_counts the request comes first, the index second.
+ * Everything a ksh_kss_selection points to is HOST memory and only read during the call. */
+typedef struct ksh_kss_selection {
+  size_t struct_size;            /* sizeof(ksh_kss_selection) of the caller's header, as ksh_comm_fns::struct_size */
+  const int32_t* cols;           /* n_cols distinct node ids, any order, 1..128; NULL: all nodes in order (n_cols is
+                                    ignored; refused on an index of more than 128 nodes) */
+  int32_t n_cols;
+  int32_t min_count, max_count;  /* 1 <= min_count <= max_count <= n_cols; max_count == 0 means n_cols */
+  const int32_t* require;        /* node ids, each one of cols: q must be in Get(id) */
+  int32_t n_require;
+  const int32_t* exclude;        /* node ids, each one of cols: q must not be in Get(id) */
+  int32_t n_exclude;
+} ksh_kss_selection;
+/* The size of a selection, its bucket offsets and the multiplicity spectrum; any of the three outputs may be NULL,
+ * not all of them.
+ * d_offsets (device, int64[2^N + 1]): the bucket offsets of the selection, as a ksh_set_view has them.
+ * n_keys (host): the selection's size.
+ * spectrum (HOST, int64[n_cols + 1]): spectrum[m] = the number of distinct k-mers of the whole structure with
+ * c(q) == m, whatever the thresholds, require and exclude say; spectrum[0] counts the k-mers that only nodes outside
+ * cols hold.  So sum(spectrum) is the n_distinct of ksh_kss_pair_counts and sum(m * spectrum[m]) the trace of its
+ * table.  All counts are exact at any structure size: they are kept in 64-bit counters throughout.
+ * The call synchronises the index's context stream once.  Scratch: the context's pool (given back before the call
+ * returns) and, for the scan of more than 2^18 buckets, its arena. */
+int ksh_kss_select_count(const ksh_kss_selection* sel, ksh_kss_index* idx, int64_t* d_offsets, int64_t* n_keys,
+                         int64_t* spectrum);
+/* The selected keys: the same pass again, with d_offsets as ksh_kss_select_count of the same request and index made
+ * them.  Bucket b goes to d_keys[d_offsets[b] .. d_offsets[b + 1]) in the index's key width, ascending, so that
+ * (d_offsets, d_keys, n_keys) is an ordinary ksh_set_view that every other call accepts (as for every set, a key
+ * buffer should be at least 16 bytes: the merge kernels read, never write, up to 16 bytes past a short set).
+ * n_keys is the capacity of d_keys in keys: nothing is written at or beyond it, nor outside a bucket's own range, nor
+ * beyond a bucket's last key.  The pass counts again as it goes: if some bucket's selection is not exactly
+ * d_offsets[b + 1] - d_offsets[b] keys inside [0, n_keys) -- offsets of another selection or index -- the call
+ * returns KSH_FAILED_PRECONDITION with a message, after its one synchronisation; d_keys is then unspecified within
+ * [0, n_keys).  n_keys == 0 with all-zero offsets is KSH_OK: nothing is written and d_keys may be NULL.
+ * KSH_INVALID_ARGUMENT for both calls, each with a message that names the field.  Before the index is dereferenced:
+ * NULL sel or idx; struct_size smaller than the struct up to n_exclude; n_cols outside [1, 128] with non-NULL cols;
+ * min_count < 1, max_count < 0, or a non-zero max_count < min_count; a negative n_require or n_exclude, or a NULL
+ * list with a positive count; all three outputs NULL (count); NULL d_offsets, a negative n_keys, NULL d_keys with
+ * n_keys > 0 (keys).  After reading only the index's host fields: an id outside [0, n_nodes); a repeated id in cols;
+ * a require or exclude id that is not in cols; an id in both require and exclude; max_count or min_count above
+ * n_cols; NULL cols on an index of more than 128 nodes.  The index still serves after a refusal.
+ * ksh_kss_index_routes reports KSH_QROUTE_PAIR_SPLIT for the last call with the meaning it has for
+ * ksh_kss_pair_counts: some bucket was cut by key range.  The index must be usable as for ksh_kss_index_query. */
+int ksh_kss_select_keys(const ksh_kss_selection* sel, ksh_kss_index* idx, const int64_t* d_offsets, int64_t n_keys,
+                        void* d_keys);
 
 #ifdef __cplusplus
 }

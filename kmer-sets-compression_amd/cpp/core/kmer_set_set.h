@@ -337,7 +337,52 @@ class KmerSetSetIndex {
     return d_counts.ToHost<std::int64_t>(n * n);
   }
 
+  // The k-mers q with min_count <= c(q) <= max_count, c(q) = the number of a with q in Get(cols[a]), that are in
+  // Get(r) for every r of `require` and in no Get(x) of `exclude` (ksh_kss_select_count + ksh_kss_select_keys): one
+  // pass over the node sets each, no Get(i) is formed.  At most 128 distinct node ids in `cols`, any order; empty
+  // `cols`: all nodes (refused above 128 nodes); max_count == 0: the number of columns.  The core of cols is
+  // Select(cols, cols.size(), 0), the k-mers private to s are Select(cols, 1, 1, {s}).
+  KmerSet<K, N, KeyType> Select(const std::vector<int>& cols, int min_count = 1, int max_count = 0,
+                                const std::vector<int>& require = {}, const std::vector<int>& exclude = {}) const {
+    using Set = KmerSet<K, N, KeyType>;
+    const std::vector<std::int32_t> ids(cols.begin(), cols.end()), req(require.begin(), require.end()),
+        exc(exclude.begin(), exclude.end());
+    const ksh_kss_selection sel = Selection(ids, min_count, max_count, req, exc);
+    ksc::DeviceBuffer off(std::size_t(Set::kBucketsNum + 1) * 8);
+    std::int64_t n = 0;
+    ksc::Check(ksh_kss_select_count(&sel, index_, static_cast<std::int64_t*>(off.get()), &n, nullptr));
+    ksc::DeviceBuffer keys(std::max<std::size_t>(std::size_t(n) * Set::kDeviceKeyBytes, 16));
+    ksc::Check(ksh_kss_select_keys(&sel, index_, static_cast<const std::int64_t*>(off.get()), n, keys.get()));
+    return Set::FromDevice(std::move(off), std::move(keys), n);
+  }
+
+  // Element m: the number of distinct k-mers of the whole structure that exactly m of the sets Get(cols[a]) hold
+  // (element 0: those that only nodes outside cols hold); cols.size() + 1 elements.  Empty `cols`: all nodes.
+  std::vector<std::int64_t> Spectrum(const std::vector<int>& cols = {}) const {
+    const std::vector<std::int32_t> ids(cols.begin(), cols.end());
+    const ksh_kss_selection sel = Selection(ids, 1, 0, {}, {});
+    const std::size_t n = ids.empty() ? std::size_t(nodes_) : ids.size();
+    std::vector<std::int64_t> spectrum((n < 128 ? n : 128) + 1, 0);  // (what the call refuses is never written)
+    ksc::Check(ksh_kss_select_count(&sel, index_, nullptr, nullptr, spectrum.data()));
+    return spectrum;
+  }
+
  private:
+  static ksh_kss_selection Selection(const std::vector<std::int32_t>& ids, int min_count, int max_count,
+                                     const std::vector<std::int32_t>& req, const std::vector<std::int32_t>& exc) {
+    ksh_kss_selection sel{};
+    sel.struct_size = sizeof(sel);
+    sel.cols = ids.empty() ? nullptr : ids.data();
+    sel.n_cols = static_cast<std::int32_t>(ids.size());
+    sel.min_count = min_count;
+    sel.max_count = max_count;
+    sel.require = req.data();
+    sel.n_require = static_cast<std::int32_t>(req.size());
+    sel.exclude = exc.data();
+    sel.n_exclude = static_cast<std::int32_t>(exc.size());
+    return sel;
+  }
+
   ksh_kss_index* index_ = nullptr;
   std::int32_t words_ = 0, nodes_ = 0;
 };

@@ -14,38 +14,17 @@
 //      rows into one 64-bit ballot per column and adds popcount(mask[a] & mask[b]) for a <= b into the
 //      workgroup's 32-bit counters in LDS, which are flushed to d_counts by 64-bit atomicAdd;
 //   3. k_pair_mirror: the lower triangle from the upper.
-#include "ksh_internal.h"
+#include "ksh_rowtile.h"
 
 #include <algorithm>
 
+using namespace ksh::pc;
+
 namespace {
 
-constexpr int kMaxCols = 128;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kTile = 512;             // entries of a tile that is not a single key
-constexpr int kSlots = 2 * kTile;      // table slots: at most half load (a single-key tile fills one slot)
-constexpr int64_t kRowsPerGroup = 8192;  // a workgroup is only started for this many entries (it zeroes and
-                                         // flushes up to 8256 counters whatever it counted)
 // Counters are 32 bits wide and a tile adds at most max(kTile, 1024) to one (a single key: one entry per node), so
 // flushing once the rows since the last flush reach this keeps every counter below 2^31.
 constexpr int64_t kFlushCap = (int64_t(1) << 31) - 2048;
-constexpr unsigned long long kEmpty = ~0ull;  // no key: keys have at most 2K - N <= 62 bits
-
-struct ColList {
-  int32_t id[kMaxCols];
-};
-
-struct PoolBuf {
-  ksh_ctx* ctx;
-  void* p = nullptr;
-  explicit PoolBuf(ksh_ctx* c) : ctx(c) {}
-  ~PoolBuf() {
-    if (p) ksh::pool_free(ctx, p);  // (single stream: a later user of the block is ordered after this call's kernels)
-  }
-  PoolBuf(const PoolBuf&) = delete;
-  PoolBuf& operator=(const PoolBuf&) = delete;
-};
 
 inline int tri(int n) { return n * (n + 1) / 2; }
 
@@ -72,80 +51,11 @@ __global__ __launch_bounds__(256) void k_pair_project(const uint64_t* __restrict
   proj[2 * j + 1] = w[1];
 }
 
-__device__ __forceinline__ uint64_t pc_uniform(uint64_t v) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(v >> 32));
-  return (uint64_t(hi) << 32) | lo;
-}
-
-// Sum of v over the workgroup, the same in every thread (two barriers; s_red: kWaves + 1 words).
-__device__ __forceinline__ int64_t pc_block_sum(int64_t v, unsigned long long* s_red) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = static_cast<unsigned long long>(v);
-  __syncthreads();
-  int64_t t = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; w++) t += static_cast<int64_t>(s_red[w]);
-  __syncthreads();
-  return t;
-}
-
-__device__ __forceinline__ uint64_t pc_block_min(uint64_t v, unsigned long long* s_red) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint64_t o = __shfl_xor(v, d, 64);
-    v = o < v ? o : v;
-  }
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint64_t t = s_red[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; w++) t = s_red[w] < t ? s_red[w] : t;
-  __syncthreads();
-  return t;
-}
-
-// s_pre[0 .. n) holds a count per node; on return s_pre[0 .. n] is their exclusive prefix (s_pre[n] = the sum,
-// also returned).  Thread t scans the nodes t * per .. (t + 1) * per.
-__device__ __forceinline__ int pc_prefix(int* s_pre, int n, unsigned long long* s_red) {
-  const int per = (n + kThreads - 1) / kThreads;
-  const int j0 = min(int(threadIdx.x) * per, n), j1 = min(j0 + per, n);
-  int mine = 0;
-  for (int j = j0; j < j1; j++) mine += s_pre[j];
-  int inc = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d, 64);
-    if (int(threadIdx.x & 63) >= d) inc += o;
-  }
-  if ((threadIdx.x & 63) == 63) s_red[threadIdx.x >> 6] = static_cast<unsigned long long>(inc);
-  __syncthreads();
-  int base = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; w++) {
-    const int s = int(s_red[w]);
-    if (w < int(threadIdx.x >> 6)) base += s;
-    total += s;
-  }
-  int run = base + inc - mine;
-  for (int j = j0; j < j1; j++) {
-    const int c = s_pre[j];
-    s_pre[j] = run;
-    run += c;
-  }
-  if (threadIdx.x == 0) s_pre[n] = total;
-  __syncthreads();
-  return total;
-}
-
-__device__ __forceinline__ uint64_t pc_mix(uint64_t x) {  // (keys of a tile share their high bits)
-  x ^= x >> 29;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 32;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 29;
-  return x;
+int pair_project(ksh_ctx* ctx, const IndexShape& x, const ColList& cols, int n_cols, uint64_t* proj) {
+  hipLaunchKernelGGL(k_pair_project, dim3(unsigned((x.n_nodes + 255) / 256)), dim3(256), 0, ctx->stream, x.d_anc,
+                     x.wt, x.n_nodes, cols, n_cols, proj);
+  KSH_HIP(hipGetLastError());
+  return KSH_OK;
 }
 
 // Adds the workgroup's counters to the table (upper triangle) and zeroes them.  Callers put a barrier before it
@@ -183,11 +93,8 @@ __global__ __launch_bounds__(kThreads) void k_pair_gram(const NodeRef* __restric
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n_cnt = n_cols * (n_cols + 1) / 2;
-  for (int t = tid; t < kSlots; t += kThreads) {
-    t_key[t] = kEmpty;
-    t_row[2 * t] = 0;
-    t_row[2 * t + 1] = 0;
-  }
+  const TileWalk w{t_key, t_row, s_cur, s_end, s_red, s_pre};
+  pc_table_clear(w);
   for (int t = tid; t < n_cnt; t += kThreads) s_cnt[t] = 0;
   __syncthreads();
 
@@ -197,56 +104,10 @@ __global__ __launch_bounds__(kThreads) void k_pair_gram(const NodeRef* __restric
   bool pending = false;   // the counters are flushed before the next tile is counted
 
   for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    int64_t mine = 0;
-    for (int j = tid; j < n_nodes; j += kThreads) {
-      const int64_t* off = nodes[j].off;
-      const int64_t c = off[b], e = off[b + 1];
-      s_cur[j] = c;
-      s_end[j] = e;
-      mine += e - c;
-    }
-    int64_t left = pc_block_sum(mine, s_red);  // entries of the bucket not yet counted
+    int64_t left = pc_bucket_begin(nodes, n_nodes, b, w);  // entries of the bucket not yet counted
     bool cut = false;
     while (left > 0) {
-      int total;
-      if (left <= kTile) {
-        for (int j = tid; j < n_nodes; j += kThreads) s_pre[j] = int(s_end[j] - s_cur[j]);
-        __syncthreads();
-        total = pc_prefix(s_pre, n_nodes, s_red);
-      } else {
-        // the next cut: all remaining entries with key <= k_min + d.  d is guessed from the density of what is
-        // left and halved while the tile does not fit; d == 0 is one key, at most one entry per node: accepted
-        if (!cut && tid == 0) flags[1] = 1;
-        cut = true;
-        uint64_t m = ~uint64_t(0);
-        for (int j = tid; j < n_nodes; j += kThreads) {
-          if (s_cur[j] < s_end[j]) {
-            const uint64_t v = static_cast<const KeyT*>(nodes[j].keys)[s_cur[j]];
-            m = v < m ? v : m;
-          }
-        }
-        const uint64_t k_min = pc_block_min(m, s_red);
-        const uint64_t span = key_max - k_min;
-        const double guess = (double(span) + 1.0) * (0.75 * kTile) / double(left);
-        uint64_t d = guess >= double(span) ? span : uint64_t(guess);
-        for (;;) {
-          const uint64_t c = k_min + d;
-          for (int j = tid; j < n_nodes; j += kThreads) {
-            const KeyT* keys = static_cast<const KeyT*>(nodes[j].keys);
-            const int64_t lo0 = s_cur[j];
-            int64_t lo = lo0, hi = min(s_end[j], lo0 + kTile + 1);  // (more than kTile of one node: no fit anyway)
-            while (lo < hi) {
-              const int64_t mid = (lo + hi) >> 1;
-              if (uint64_t(keys[mid]) <= c) lo = mid + 1; else hi = mid;
-            }
-            s_pre[j] = int(lo - lo0);
-          }
-          __syncthreads();
-          total = pc_prefix(s_pre, n_nodes, s_red);
-          if (total <= kTile || d == 0) break;
-          d >>= 1;
-        }
-      }
+      const int total = pc_tile_cut<KeyT>(nodes, n_nodes, w, left, key_max, &cut, flags);
 
       if (pending) {  // (uniform: rows_acc is)
         pc_flush(s_cnt, n_cols, counts);
@@ -256,27 +117,7 @@ __global__ __launch_bounds__(kThreads) void k_pair_gram(const NodeRef* __restric
         __syncthreads();
       }
 
-      // the tile's entries into the table: entry e belongs to the node j with s_pre[j] <= e < s_pre[j + 1]
-      for (int e = tid; e < total; e += kThreads) {
-        int lo = 0, hi = n_nodes - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (s_pre[mid] <= e) lo = mid; else hi = mid - 1;
-        }
-        const int j = lo;
-        const unsigned long long key = static_cast<const KeyT*>(nodes[j].keys)[s_cur[j] + (e - s_pre[j])];
-        const uint64_t p0 = proj[2 * j], p1 = proj[2 * j + 1];
-        uint32_t h = uint32_t(pc_mix(key)) & (kSlots - 1);
-        for (;;) {
-          const unsigned long long prev = atomicCAS(&t_key[h], kEmpty, key);
-          if (prev == kEmpty || prev == key) break;
-          h = (h + 1) & (kSlots - 1);
-        }
-        if (p0) atomicOr(&t_row[2 * h], static_cast<unsigned long long>(p0));
-        if (p1) atomicOr(&t_row[2 * h + 1], static_cast<unsigned long long>(p1));
-      }
-      __syncthreads();
-      for (int j = tid; j < n_nodes; j += kThreads) s_cur[j] += s_pre[j + 1] - s_pre[j];
+      pc_tile_fill<KeyT>(nodes, n_nodes, proj, w, total);
 
       // Gram: a wave takes 64 slots, a lane a slot (an empty slot is a zero row), and leaves them empty
       unsigned long long* mask = s_mask + wave * kMaxCols;
@@ -401,9 +242,7 @@ extern "C" int ksh_kss_pair_counts(const int32_t* cols, int32_t n_cols, ksh_kss_
   KSH_HIP(hipMemsetAsync(x.d_flags, 0, 16, ctx->stream));
   KSH_HIP(hipMemsetAsync(distinct, 0, 8, ctx->stream));
   KSH_HIP(hipMemsetAsync(d_counts, 0, size_t(n_cols) * size_t(n_cols) * 8, ctx->stream));
-  hipLaunchKernelGGL(k_pair_project, dim3(unsigned((x.n_nodes + 255) / 256)), dim3(256), 0, ctx->stream, x.d_anc,
-                     x.wt, x.n_nodes, list, n_cols, proj);
-  KSH_HIP(hipGetLastError());
+  KSH_TRY(pair_project(ctx, x, list, n_cols, proj));
   const int64_t flush = flush_rows > 0 ? std::min(flush_rows, kFlushCap) : kFlushCap;
   KSH_TRY(KSH_BY_KEY(x.g.key_bytes, launch_gram, ctx, x, proj, n_cols, flush, d_counts, distinct));
   hipLaunchKernelGGL(k_pair_mirror, dim3(unsigned((n_cols * n_cols + 255) / 256)), dim3(256), 0, ctx->stream,

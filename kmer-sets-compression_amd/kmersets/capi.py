@@ -59,6 +59,13 @@ class PairJob(C.Structure):
                 ("d_keys_bma", C.c_void_p), ("totals", C.c_int64 * 3)]
 
 
+class Selection(C.Structure):
+    """ksh_kss_selection; the lists are host arrays of int32 node ids."""
+    _fields_ = [("struct_size", C.c_size_t), ("cols", C.POINTER(C.c_int32)), ("n_cols", C.c_int32),
+                ("min_count", C.c_int32), ("max_count", C.c_int32), ("require", C.POINTER(C.c_int32)),
+                ("n_require", C.c_int32), ("exclude", C.POINTER(C.c_int32)), ("n_exclude", C.c_int32)]
+
+
 def build(force=False):
     """Compiles the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC_DIR, f) for f in os.listdir(CSRC_DIR) if f.endswith((".hip", ".h"))]
@@ -186,6 +193,8 @@ def lib():
         "ksh_kss_index_destroy": (C.c_int, [vp]),
         "ksh_seq_hits": (C.c_int, [C.POINTER(SpssView), vp, C.c_int, C.c_int, i64, vp]),
         "ksh_kss_pair_counts": (C.c_int, [C.POINTER(i32), i32, vp, i64, vp, C.POINTER(i64)]),
+        "ksh_kss_select_count": (C.c_int, [C.POINTER(Selection), vp, vp, C.POINTER(i64), C.POINTER(i64)]),
+        "ksh_kss_select_keys": (C.c_int, [C.POINTER(Selection), vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1119,6 +1128,72 @@ class KssIndex:
                                         C.byref(distinct) if with_distinct else None))
         out = counts if device else counts.cpu().numpy()
         return (out, distinct.value) if with_distinct else out
+
+    def _selection(self, cols, min_count, max_count, require, exclude):
+        """(ksh_kss_selection, n_cols, the arrays it points to -- keep them alive for the call)."""
+        def ids(x):
+            arr = np.ascontiguousarray(x, dtype=np.int32).reshape(-1)
+            return arr, int(arr.size), (arr if arr.size else np.zeros(1, dtype=np.int32)).ctypes.data_as(
+                C.POINTER(C.c_int32))  # (never NULL: an empty list is a count of 0)
+        if cols is None:
+            keep_c, n_cols, p_cols = None, self.n_nodes, None
+        else:
+            keep_c, n_cols, p_cols = ids(cols)
+        keep_r, n_req, p_req = ids(require)
+        keep_x, n_exc, p_exc = ids(exclude)
+        sel = Selection(C.sizeof(Selection), p_cols, n_cols if cols is not None else 0, int(min_count),
+                        0 if max_count is None else int(max_count), p_req, n_req, p_exc, n_exc)
+        return sel, n_cols, (keep_c, keep_r, keep_x)
+
+    def select_count(self, cols=None, min_count=1, max_count=None, require=(), exclude=(), offsets=True,
+                     size=True, spectrum=False):
+        """ksh_kss_select_count, the raw call: (offsets, n_keys, spectrum) of the selection -- a device int64
+        tensor [2^N + 1], an int, an np.int64 array [n_cols + 1] -- each None where its flag is False."""
+        import torch
+
+        with torch.cuda.stream(self.ctx.stream):
+            h = self._handle()
+            sel, n_cols, keep = self._selection(cols, min_count, max_count, require, exclude)
+            off = torch.empty((1 << self.g.n_bucket_bits) + 1, dtype=torch.int64, device=self.ctx.device) \
+                if offsets else None
+            n = C.c_int64()
+            spec = np.zeros(min(max(n_cols, 1), 128) + 1, dtype=np.int64)  # (what the call refuses is never written)
+            check(lib().ksh_kss_select_count(C.byref(sel), h, off.data_ptr() if offsets else None,
+                                             C.byref(n) if size else None,
+                                             spec.ctypes.data_as(C.POINTER(C.c_int64)) if spectrum else None))
+            del keep
+            return off, (n.value if size else None), (spec if spectrum else None)
+
+    def select_write(self, offsets, n_keys, keys, cols=None, min_count=1, max_count=None, require=(), exclude=()):
+        """ksh_kss_select_keys, the raw call: writes the selection's keys into `keys` (a device tensor of at least
+        n_keys keys, or None with n_keys == 0) at the bucket offsets `offsets`; n_keys is the capacity in keys."""
+        import torch
+
+        with torch.cuda.stream(self.ctx.stream):
+            h = self._handle()
+            sel, n_cols, keep = self._selection(cols, min_count, max_count, require, exclude)
+            check(lib().ksh_kss_select_keys(C.byref(sel), h, offsets.data_ptr() if offsets is not None else None,
+                                            int(n_keys), keys.data_ptr() if keys is not None else None))
+            del keep
+
+    def select(self, cols=None, min_count=1, max_count=None, require=(), exclude=()):
+        """The k-mers q held by any node with min_count <= c(q) <= max_count (c(q) = the number of a with q in
+        Get(cols[a]); max_count None: n_cols), in Get(r) for every r of require and in no Get(x) of exclude, as a
+        DeviceSet that every other call accepts.  cols: up to 128 distinct node ids (None: all nodes); require and
+        exclude: ids out of cols.  The core of cols is min_count = len(cols); the k-mers private to s are
+        require=[s], max_count=1."""
+        import torch
+
+        off, n, _ = self.select_count(cols, min_count, max_count, require, exclude)
+        with torch.cuda.stream(self.ctx.stream):
+            keys = torch.empty(max(n * self.g.key_bytes, 16), dtype=torch.uint8, device=self.ctx.device)
+        self.select_write(off, n, keys, cols, min_count, max_count, require, exclude)
+        return DeviceSet(self.g, off, keys, n)
+
+    def spectrum(self, cols=None):
+        """np.int64[n_cols + 1]: element m is the number of distinct k-mers of the whole structure that exactly m of
+        the sets Get(cols[a]) hold (element 0: those that only nodes outside cols hold)."""
+        return self.select_count(cols, offsets=False, size=False, spectrum=True)[2]
 
     def jaccard(self, cols=None):
         """Exact Jaccard similarities c_ab / (c_aa + c_bb - c_ab) of the sets Get(cols[a]), a float64 numpy array
