@@ -168,7 +168,7 @@ int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
  * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
  * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
  * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
- * ksh_kss_select_keys and the accessors of a ksh_kss /
+ * ksh_kss_select_keys, ksh_kss_color_classes and the accessors of a ksh_kss /
  * ksh_kss_index, plans and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
  * plan: nothing else uses their slot.
  *
@@ -617,8 +617,8 @@ int ksh_kss_index_query(ksh_kss_index* idx, const uint64_t* d_kmers, int64_t n, 
 /* n_nodes, W, and the bytes of the resident sets the index reads (offsets included). */
 int ksh_kss_index_info(const ksh_kss_index* idx, int32_t* n_nodes, int32_t* words_per_row,
                        int64_t* resident_bytes);
-/* The routes the last query (ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count or
- * ksh_kss_select_keys) took, a mask of KSH_QROUTE_* (synchronises the stream). */
+/* The routes the last query (ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
+ * ksh_kss_select_keys or ksh_kss_color_classes) took, a mask of KSH_QROUTE_* (synchronises the stream). */
 enum {
   KSH_QROUTE_SEARCH = 1 << 0,    /* per-query search                                            */
   KSH_QROUTE_JOIN = 1 << 1,      /* bucket join                                                  */
@@ -626,8 +626,11 @@ enum {
   KSH_QROUTE_CHUNKED = 1 << 3,   /* ... the batch took more than one pass of 2^24 queries        */
   KSH_QROUTE_SEQ_PASSES = 1 << 4, /* ksh_seq_hits: the batch took more than one pass of positions */
   KSH_QROUTE_PAIR_SPLIT = 1 << 5, /* ksh_kss_pair_counts, ksh_kss_select_count, ksh_kss_select_keys: some bucket's
-                                     k-mers did not fit one tile and were cut by key range        */
-  KSH_QROUTE_PAIR_FLUSH = 1 << 6  /* ... some workgroup flushed its counters before its last tile */
+                                     k-mers did not fit one tile and were cut by key range (ksh_kss_color_classes
+                                     reports it with the same meaning)                            */
+  KSH_QROUTE_PAIR_FLUSH = 1 << 6, /* ... some workgroup flushed its counters before its last tile */
+  KSH_QROUTE_CLASS_SPILL = 1 << 7 /* ksh_kss_color_classes: some workgroup emptied its on-chip class table into
+                                     the global one before its last tile                          */
 };
 int ksh_kss_index_routes(const ksh_kss_index* idx, uint32_t* bits);
 int ksh_kss_index_destroy(ksh_kss_index* idx);
@@ -737,6 +740,39 @@ int ksh_kss_select_count(const ksh_kss_selection* sel, ksh_kss_index* idx, int64
  * ksh_kss_pair_counts: some bucket was cut by key range.  The index must be usable as for ksh_kss_index_query. */
 int ksh_kss_select_keys(const ksh_kss_selection* sel, ksh_kss_index* idx, const int64_t* d_offsets, int64_t n_keys,
                         void* d_keys);
+
+/* ---- Colour classes: the k-mers of a KmerSetSet per exact membership pattern --------------------------------
+ * For a k-mer q held by any node of the index, its row over the chosen columns has bit a set iff q is in
+ * Get(cols[a]).  A colour class is a distinct row; the call returns every class with the number of distinct k-mers
+ * of the structure that have exactly that row: the data of an UpSet plot, the private k-mers of every set at once
+ * (the classes with one bit), the split support of a phylogeny, the colour-class table of a coloured de Bruijn
+ * graph.  The multiplicity spectrum of ksh_kss_select_count is its sum by popcount, the table of ksh_kss_pair_counts
+ * its sum over the classes that hold two given bits.  One pass over the index's resident node sets (the pass of
+ * ksh_kss_pair_counts with another consumer): nothing is decompressed and no Get(i) is formed.
+ * cols, n_cols: as in ksh_kss_pair_counts -- a HOST array of 1..128 distinct node ids in any order (internal nodes
+ * are allowed), only read during the call; NULL: all nodes in order (n_cols is ignored), refused on an index of more
+ * than 128 nodes.
+ * capacity: the classes the caller has room for, 1 <= capacity <= 2^24.  rows: HOST uint64[2 * capacity]; counts:
+ * HOST int64[capacity]; n_classes: host.
+ * On KSH_OK *n_classes <= capacity classes are written and nothing beyond them: class c has rows[2 c] = the bits of
+ * columns 0..63, rows[2 c + 1] = the bits of columns 64..127, and counts[c] >= 1.  Classes are ascending by
+ * (rows[2 c + 1], rows[2 c]) read as one 128-bit integer.  Row zero is a class like any other: the k-mers that only
+ * nodes outside cols hold (what spectrum[0] counts), so sum(counts) is the n_distinct of ksh_kss_pair_counts.  An
+ * index without k-mers gives *n_classes = 0.  All counts are exact at any structure size: 64-bit counters throughout.
+ * More classes than capacity: KSH_FAILED_PRECONDITION with a message that names capacity, *n_classes = capacity + 1,
+ * rows and counts unspecified within their first capacity entries and untouched beyond them; the index still serves.
+ * KSH_INVALID_ARGUMENT, each with a message that names the field.  Before the index is dereferenced: NULL idx, rows,
+ * counts or n_classes; capacity outside [1, 2^24]; n_cols outside [1, 128] with non-NULL cols.  After reading only
+ * the index's host fields: an id outside [0, n_nodes); a repeated id; NULL cols on an index of more than 128 nodes.
+ * The call is stateless: scratch comes from the context's pool (16 bytes per node, 32 bytes per slot of a table of
+ * the next power of two >= 2 * capacity slots, 24 bytes per class of capacity) and is given back before the call
+ * returns; it keeps no plan, joins no plan group and ends no pending plan.  As in ksh_kss_pair_counts the request
+ * comes first and the index third.  It synchronises the index's context stream once; a table of more than 4096
+ * classes takes a second copy and synchronisation for the classes beyond them.
+ * ksh_kss_index_routes reports KSH_QROUTE_PAIR_SPLIT (as for ksh_kss_pair_counts) and KSH_QROUTE_CLASS_SPILL for the
+ * last call.  The index must be usable as for ksh_kss_index_query. */
+int ksh_kss_color_classes(const int32_t* cols, int32_t n_cols, ksh_kss_index* idx, int64_t capacity, uint64_t* rows,
+                          int64_t* counts, int64_t* n_classes);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@
 #define KSC_CORE_KMER_SET_SET_H_
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <filesystem>
@@ -365,6 +366,40 @@ class KmerSetSetIndex {
     std::vector<std::int64_t> spectrum((n < 128 ? n : 128) + 1, 0);  // (what the call refuses is never written)
     ksc::Check(ksh_kss_select_count(&sel, index_, nullptr, nullptr, spectrum.data()));
     return spectrum;
+  }
+
+  // A colour class: a distinct membership pattern over the chosen columns (bit a % 64 of row[a / 64]: the class's
+  // k-mers are in Get(cols[a])) and the number of distinct k-mers of the structure with exactly that pattern.
+  struct ColorClass {
+    std::array<std::uint64_t, 2> row;
+    std::int64_t count;
+  };
+  // Every colour class of `cols` (ksh_kss_color_classes), ascending by (row[1], row[0]); the zero row counts the
+  // k-mers that only nodes outside cols hold.  At most 128 distinct node ids in any order; empty `cols`: all nodes
+  // (refused above 128 nodes).  capacity: the classes there is room for; 0: min(2^n, 2^16), times 4 for as long as
+  // the call answers that there are more, up to min(2^n, 2^24), where the refusal is thrown.  A given capacity is
+  // tried once.
+  std::vector<ColorClass> ColorClasses(const std::vector<int>& cols = {}, std::int64_t capacity = 0) const {
+    const std::vector<std::int32_t> ids(cols.begin(), cols.end());
+    const std::size_t n = ids.empty() ? std::size_t(nodes_) : ids.size();
+    const std::int64_t top = std::int64_t(1) << std::min<std::size_t>(n, 24);
+    std::int64_t cap = capacity > 0 ? capacity : std::min<std::int64_t>(top, std::int64_t(1) << 16);
+    for (;;) {
+      const std::size_t room = std::size_t(std::min<std::int64_t>(cap, std::int64_t(1) << 24));
+      std::vector<std::uint64_t> rows(2 * room);  // (what the call refuses is never written)
+      std::vector<std::int64_t> counts(room);
+      std::int64_t got = 0;
+      const int rc = ksh_kss_color_classes(ids.empty() ? nullptr : ids.data(), static_cast<std::int32_t>(ids.size()),
+                                           index_, cap, rows.data(), counts.data(), &got);
+      if (rc == KSH_FAILED_PRECONDITION && got == cap + 1 && capacity <= 0 && cap < top) {
+        cap = std::min<std::int64_t>(4 * cap, top);
+        continue;
+      }
+      ksc::Check(rc);
+      std::vector<ColorClass> out(static_cast<std::size_t>(got));
+      for (std::size_t c = 0; c < out.size(); c++) out[c] = ColorClass{{rows[2 * c], rows[2 * c + 1]}, counts[c]};
+      return out;
+    }
   }
 
  private:

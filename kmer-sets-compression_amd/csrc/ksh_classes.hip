@@ -1,0 +1,343 @@
+// Colour classes of a KmerSetSet on its index (ksh_kss_color_classes): for chosen nodes
+// cols[0 .. n), every distinct row of column bits (bit a = the k-mer is in Get(cols[a])) with the number of distinct
+// k-mers of the structure that have exactly that row.
+//
+// The rows are formed as in ksh_kss_pair_counts and ksh_kss_select_*: the tile walk of ksh_rowtile.h.  The consumer:
+//   wave     : a lane takes a slot of the tile's table and empties it; the occupied lanes are grouped by equal row
+//              with ballots (the leader's row, ballot(row == leader's), the leader carries the popcount), so a wave
+//              has one (row, count) per distinct row among its 64 slots;
+//   workgroup: the leaders add their pairs to a class table in LDS (kClsSlots slots of three key words and a 64-bit
+//              count).  After a tile that leaves more than kClsSpill slots occupied the workgroup adds every entry
+//              to the global table and clears its own before the next tile, and at its end what is left;
+//   global   : an open-addressing table of 2^m >= 2 * capacity slots in pool memory, packed by k_class_pack; the
+//              host sorts the packed classes.
+// Both tables take a row by the same insertion, cls_insert: three set-once words per slot, each claimed by atomicCAS
+// from 0, no lane ever waits for another, every probe loop is bounded by the table's slot count.
+#include "ksh_rowtile.h"
+
+#include <algorithm>
+#include <array>
+
+using namespace ksh::pc;
+
+namespace {
+
+constexpr int kClsSlots = 1024;                       // slots of a workgroup's class table
+constexpr int kClsSpill = kClsSlots * 3 / 4 - kTile;  // spill above this: the next tile's <= kTile new classes
+                                                      // still fit at no more than 3/4 load
+constexpr unsigned long long kValid = 1ull << 63;     // set in every written key word: 0 is "not yet written"
+constexpr int64_t kMaxCapacity = int64_t(1) << 24;
+constexpr int64_t kFirstCopy = 4096;  // classes read back with the call's one synchronisation (more: a second copy)
+// device words of a call, in front of the packed classes: [0] slots of the global table that are taken, [1] non-zero:
+// more than `capacity` classes, or a row found no slot, [2] the classes k_class_pack packed, [3] non-zero: a row
+// found no slot in a workgroup's table (cannot happen: kClsSpill)
+constexpr int kCtlWords = 4;
+
+// LDS of k_color_classes: the walk, the class table (4 words per slot), occupancy and stop flag.
+size_t classes_lds_bytes(int n_nodes) { return walk_lds_bytes(n_nodes) + size_t(kClsSlots) * 32 + 8; }
+
+}  // namespace
+
+namespace ksh {
+
+__device__ __forceinline__ uint32_t cls_hash(uint64_t r0, uint64_t r1) {
+  return uint32_t(pc_mix(r0 ^ pc_mix(r1 + 0x9E3779B97F4A7C15ull)));
+}
+
+// Adds cnt to the slot of row (r0, r1), taking an empty slot if the row has none.  Word i of slot s is
+// base[s * kStride + i * kPlane]: i = 0, 1, 2 the key, i = 3 the count.  At 128 columns every 128-bit value is a
+// row, so no row word has a value to spare for "empty" and there is no 128-bit compare-and-swap: the key is three
+// words that carry 63 bits of r0, 63 bits of r1 and the two top bits, each with kValid set, each written once, by
+// atomicCAS from 0.  A thread claims word 0; if it was 0 or is its own it claims word 1 the same way, then word 2;
+// on any other value it goes to the next slot.
+//   - Whoever writes word i of a slot goes on to word i + 1 of it, and had matched the words before i: so every
+//     slot whose word 0 is written ends with all three written, and they are the key of the thread that wrote (or
+//     first matched) word 2 -- the key of a row that was inserted, which then adds its count: no slot stays half
+//     written or with a zero count once the inserting threads are done.
+//   - A thread leaves a slot only on a word that holds another value, and words never change once written: two
+//     threads with the same row decide alike at every slot and settle on the same one.  A row has one slot.
+//   - Nobody waits for a value: a wave's lanes may insert side by side, in lockstep.
+// The loop visits every slot at most once.  Returns false when each held another row.  *claims grows by the
+// slots whose word 0 this call wrote: each is some row's new slot (not necessarily this row's).
+template <int kStride, int kPlane>
+__device__ __forceinline__ bool cls_insert(unsigned long long* base, uint32_t mask, uint64_t r0, uint64_t r1,
+                                           unsigned long long cnt, int* claims) {
+  const unsigned long long w0 = (r0 & ~kValid) | kValid, w1 = (r1 & ~kValid) | kValid;
+  const unsigned long long w2 = (r0 >> 63) | ((r1 >> 63) << 1) | kValid;
+  uint32_t h = cls_hash(r0, r1) & mask;
+  for (uint32_t probe = 0; probe <= mask; probe++, h = (h + 1) & mask) {
+    unsigned long long* s = base + size_t(h) * kStride;
+    unsigned long long prev = atomicCAS(s, 0ull, w0);
+    if (prev != 0 && prev != w0) continue;
+    if (prev == 0) *claims += 1;
+    prev = atomicCAS(s + kPlane, 0ull, w1);
+    if (prev != 0 && prev != w1) continue;
+    prev = atomicCAS(s + 2 * kPlane, 0ull, w2);
+    if (prev != 0 && prev != w2) continue;
+    atomicAdd(s + 3 * kPlane, cnt);
+    return true;
+  }
+  return false;
+}
+
+__device__ __forceinline__ unsigned long long cls_peek(const unsigned long long* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Every entry of the workgroup's table into the global one; the table is left empty.  Callers put a barrier before
+// it (the table is complete) and after it.  Once the call has failed (ctl[1]) nothing more is inserted.
+__device__ __forceinline__ void cls_spill(unsigned long long* c_tab, unsigned long long* __restrict__ g_tab,
+                                          uint32_t g_mask, int64_t capacity, unsigned long long* __restrict__ ctl) {
+  for (int s = threadIdx.x; s < kClsSlots; s += kThreads) {
+    const unsigned long long w0 = c_tab[s];
+    if (w0 == 0) continue;
+    const unsigned long long w1 = c_tab[kClsSlots + s], w2 = c_tab[2 * kClsSlots + s];
+    const unsigned long long cnt = c_tab[3 * kClsSlots + s];
+    c_tab[s] = 0;
+    c_tab[kClsSlots + s] = 0;
+    c_tab[2 * kClsSlots + s] = 0;
+    c_tab[3 * kClsSlots + s] = 0;
+    if (cls_peek(&ctl[1]) != 0) continue;
+    const uint64_t r0 = (w0 & ~kValid) | ((w2 & 1) << 63), r1 = (w1 & ~kValid) | (((w2 >> 1) & 1) << 63);
+    int claims = 0;
+    if (!cls_insert<4, 1>(g_tab, g_mask, r0, r1, cnt, &claims)) atomicAdd(&ctl[1], 1ull);
+    if (claims) {
+      const unsigned long long taken = atomicAdd(&ctl[0], static_cast<unsigned long long>(claims)) + claims;
+      if (taken > static_cast<unsigned long long>(capacity)) atomicAdd(&ctl[1], 1ull);
+    }
+  }
+}
+
+// flags[1]: some bucket was cut by key range; flags[3]: some workgroup spilled its class table before its last tile.
+template <typename KeyT>
+__global__ __launch_bounds__(kThreads) void k_color_classes(const NodeRef* __restrict__ nodes, int n_nodes,
+                                                            const uint64_t* __restrict__ proj, int64_t nb,
+                                                            int key_bits, unsigned long long* __restrict__ g_tab,
+                                                            uint32_t g_mask, int64_t capacity,
+                                                            unsigned long long* __restrict__ ctl,
+                                                            int* __restrict__ flags) {
+  extern __shared__ unsigned long long cls_lds[];
+  unsigned long long* t_key = cls_lds;
+  unsigned long long* t_row = t_key + kSlots;
+  unsigned long long* c_tab = t_row + 2 * kSlots;
+  long long* s_cur = reinterpret_cast<long long*>(c_tab + 4 * kClsSlots);
+  long long* s_end = s_cur + n_nodes;
+  unsigned long long* s_red = reinterpret_cast<unsigned long long*>(s_end + n_nodes);
+  int* s_ctl = reinterpret_cast<int*>(s_red + 8);  // [0] slots of c_tab that are taken, [1] the call has failed
+  int* s_pre = s_ctl + 2;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const TileWalk w{t_key, t_row, s_cur, s_end, s_red, s_pre};
+  pc_table_clear(w);
+  for (int t = tid; t < 4 * kClsSlots; t += kThreads) c_tab[t] = 0;
+  if (tid == 0) s_ctl[0] = s_ctl[1] = 0;
+  __syncthreads();
+
+  const uint64_t key_max = (uint64_t(1) << key_bits) - 1;
+  bool pending = false;  // the class table is spilled before the next tile is counted
+  bool lost = false;     // (cannot happen) a row found no slot in c_tab
+
+  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
+    // (written before the barriers of pc_bucket_begin and read after them; read only where a tile, and so a
+    // barrier, follows before thread 0 can write it again)
+    if (tid == 0) s_ctl[1] = cls_peek(&ctl[1]) != 0;
+    int64_t left = pc_bucket_begin(nodes, n_nodes, b, w);
+    if (left == 0) continue;  // (uniform)
+    if (s_ctl[1]) break;      // (uniform) more classes than capacity: the call fails whatever else is counted
+    bool cut = false;
+    while (left > 0) {
+      const int total = pc_tile_cut<KeyT>(nodes, n_nodes, w, left, key_max, &cut, flags);
+
+      if (pending) {  // (uniform: s_ctl[0] was read behind a barrier)
+        cls_spill(c_tab, g_tab, g_mask, capacity, ctl);
+        if (tid == 0) {
+          flags[3] = 1;
+          s_ctl[0] = 0;
+        }
+        pending = false;
+        __syncthreads();
+      }
+
+      pc_tile_fill<KeyT>(nodes, n_nodes, proj, w, total);
+
+      // a lane takes a slot and leaves it empty; one (row, count) per wave and distinct row goes to c_tab
+      for (int slot = tid; slot < kSlots; slot += kThreads) {
+        const bool occ = t_key[slot] != kEmpty;
+        uint64_t r0 = 0, r1 = 0;
+        if (occ) {
+          r0 = t_row[2 * slot];
+          r1 = t_row[2 * slot + 1];
+          t_key[slot] = kEmpty;
+          t_row[2 * slot] = 0;
+          t_row[2 * slot + 1] = 0;
+        }
+        unsigned long long todo = __ballot(occ);
+        int mine = 0;  // leaders: the lanes of this round that hold my row
+        while (todo) {
+          const int leader = __ffsll(todo) - 1;
+          const uint64_t l0 = __shfl(static_cast<unsigned long long>(r0), leader, 64);
+          const uint64_t l1 = __shfl(static_cast<unsigned long long>(r1), leader, 64);
+          const unsigned long long same = __ballot(occ && r0 == l0 && r1 == l1);
+          if (lane == leader) mine = __popcll(same);
+          todo &= ~same;
+        }
+        if (mine) {  // the leaders insert side by side: cls_insert never waits
+          int claims = 0;
+          if (!cls_insert<1, kClsSlots>(c_tab, kClsSlots - 1, r0, r1, static_cast<unsigned long long>(mine), &claims))
+            lost = true;
+          if (claims) atomicAdd(&s_ctl[0], claims);
+        }
+      }
+      __syncthreads();
+
+      left -= total;
+      pending = s_ctl[0] > kClsSpill;
+    }
+  }
+  // (the table is complete: the last barrier was a tile's, or no tile was counted)
+  cls_spill(c_tab, g_tab, g_mask, capacity, ctl);
+  if (lost) atomicAdd(&ctl[3], 1ull);
+}
+
+// The occupied slots of the global table, packed as (r0, r1, count) in any order: out[3 c ..], c < capacity;
+// ctl[2] = their number, whatever the capacity.  One atomicAdd per wave and round.
+__global__ __launch_bounds__(256) void k_class_pack(const unsigned long long* __restrict__ g_tab, int64_t slots,
+                                                    int64_t capacity, unsigned long long* __restrict__ ctl,
+                                                    unsigned long long* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t step = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t base = int64_t(blockIdx.x) * blockDim.x; base < slots; base += step) {  // (uniform trip count)
+    const int64_t s = base + threadIdx.x;
+    unsigned long long w0 = 0;
+    if (s < slots) w0 = g_tab[4 * s];
+    const unsigned long long occ = __ballot(w0 != 0);
+    if (occ == 0) continue;
+    const int leader = __ffsll(occ) - 1;
+    unsigned long long at = 0;
+    if (lane == leader) at = atomicAdd(&ctl[2], static_cast<unsigned long long>(__popcll(occ)));
+    at = __shfl(at, leader, 64) + __popcll(occ & ((1ull << lane) - 1));
+    if (w0 != 0 && at < static_cast<unsigned long long>(capacity)) {
+      const unsigned long long w1 = g_tab[4 * s + 1], w2 = g_tab[4 * s + 2];
+      out[3 * at] = (w0 & ~kValid) | ((w2 & 1) << 63);
+      out[3 * at + 1] = (w1 & ~kValid) | (((w2 >> 1) & 1) << 63);
+      out[3 * at + 2] = g_tab[4 * s + 3];
+    }
+  }
+}
+
+template <typename KeyT>
+static int launch_classes(ksh_ctx* ctx, const IndexShape& x, const uint64_t* proj, unsigned long long* g_tab,
+                          int64_t slots, int64_t capacity, unsigned long long* ctl) {
+  const size_t lds = classes_lds_bytes(x.n_nodes);
+  const uint32_t bit = 512u << (sizeof(KeyT) == 2 ? 0 : sizeof(KeyT) == 4 ? 1 : 2);
+  if (lds > (64u << 10) && !(ctx->lds_opt_in & bit)) {  // (more than the 64 KB a kernel gets without asking)
+    KSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_color_classes<KeyT>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, int(classes_lds_bytes(1024))));
+    ctx->lds_opt_in |= bit;
+  }
+  int n_cu = 0;
+  KSH_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  const int64_t nb = n_buckets(&x.g);
+  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, int64_t(160 << 10) / int64_t(lds)));
+  const int64_t want = (x.total_keys + kRowsPerGroup - 1) / kRowsPerGroup;
+  const int64_t grid = std::max<int64_t>(1, std::min({want, nb, per_cu * n_cu}));
+  hipLaunchKernelGGL((k_color_classes<KeyT>), dim3(unsigned(grid)), dim3(kThreads), lds, ctx->stream,
+                     static_cast<const NodeRef*>(x.d_nodes), x.n_nodes, proj, nb, key_bits(&x.g), g_tab,
+                     uint32_t(slots - 1), capacity, ctl, x.d_flags);
+  KSH_HIP(hipGetLastError());
+  return KSH_OK;
+}
+
+}  // namespace ksh
+
+using namespace ksh;
+
+extern "C" int ksh_kss_color_classes(const int32_t* cols, int32_t n_cols, ksh_kss_index* idx, int64_t capacity,
+                                     uint64_t* rows, int64_t* counts, int64_t* n_classes) {
+  if (!idx) return fail(KSH_INVALID_ARGUMENT, "idx is NULL");
+  if (!rows) return fail(KSH_INVALID_ARGUMENT, "rows is NULL");
+  if (!counts) return fail(KSH_INVALID_ARGUMENT, "counts is NULL");
+  if (!n_classes) return fail(KSH_INVALID_ARGUMENT, "n_classes is NULL");
+  if (capacity < 1 || capacity > kMaxCapacity)
+    return fail(KSH_INVALID_ARGUMENT, "capacity = %lld is outside [1, %lld]", (long long)capacity,
+                (long long)kMaxCapacity);
+  if (cols && (n_cols < 1 || n_cols > kMaxCols))
+    return fail(KSH_INVALID_ARGUMENT, "n_cols = %d is outside [1, %d]", n_cols, kMaxCols);
+  const IndexShape x = index_shape(idx);
+  ColList list{};
+  if (!cols) {
+    if (x.n_nodes > kMaxCols)
+      return fail(KSH_INVALID_ARGUMENT, "cols is NULL (all nodes) but the index has %d nodes, more than %d columns: "
+                                        "name the columns of each call", x.n_nodes, kMaxCols);
+    n_cols = x.n_nodes;
+    for (int32_t c = 0; c < n_cols; c++) list.id[c] = c;
+  } else {
+    std::vector<char> seen(size_t(x.n_nodes), 0);
+    for (int32_t c = 0; c < n_cols; c++) {
+      const int32_t id = cols[c];
+      if (id < 0 || id >= x.n_nodes)
+        return fail(KSH_INVALID_ARGUMENT, "cols[%d] = %d is outside [0, %d)", c, id, x.n_nodes);
+      if (seen[size_t(id)]) return fail(KSH_INVALID_ARGUMENT, "cols[%d] = %d is repeated", c, id);
+      seen[size_t(id)] = 1;
+      list.id[c] = id;
+    }
+  }
+  ksh_ctx* ctx = x.ctx;
+  KSH_HIP(hipSetDevice(ctx->device));
+  int64_t slots = 2;
+  while (slots < 2 * capacity) slots <<= 1;
+  PoolBuf proj(ctx), tab(ctx), res(ctx);
+  KSH_TRY(pool_alloc(ctx, size_t(std::max(x.n_nodes, 1)) * 16, &proj.p));
+  KSH_TRY(pool_alloc(ctx, size_t(slots) * 32, &tab.p));
+  KSH_TRY(pool_alloc(ctx, (size_t(kCtlWords) + 3 * size_t(capacity)) * 8, &res.p));
+  auto* g_tab = static_cast<unsigned long long*>(tab.p);
+  auto* ctl = static_cast<unsigned long long*>(res.p);
+  index_set_routes(idx, 0);
+  KSH_HIP(hipMemsetAsync(x.d_flags, 0, 16, ctx->stream));
+  KSH_HIP(hipMemsetAsync(g_tab, 0, size_t(slots) * 32, ctx->stream));
+  KSH_HIP(hipMemsetAsync(ctl, 0, size_t(kCtlWords) * 8, ctx->stream));
+  KSH_TRY(pair_project(ctx, x, list, n_cols, static_cast<uint64_t*>(proj.p)));
+  KSH_TRY(KSH_BY_KEY(x.g.key_bytes, launch_classes, ctx, x, static_cast<const uint64_t*>(proj.p), g_tab, slots,
+                     capacity, ctl));
+  const int64_t pack_grid = std::max<int64_t>(1, std::min<int64_t>((slots + 255) / 256, 4096));
+  hipLaunchKernelGGL(k_class_pack, dim3(unsigned(pack_grid)), dim3(256), 0, ctx->stream, g_tab, slots, capacity, ctl,
+                     ctl + kCtlWords);
+  KSH_HIP(hipGetLastError());
+
+  // the call's one synchronisation brings the control words and the first kFirstCopy classes
+  const int64_t first = std::min(capacity, kFirstCopy);
+  const size_t first_words = size_t(kCtlWords) + 3 * size_t(first);
+  int64_t* h = nullptr;
+  KSH_TRY(pinned_words(ctx, first_words, &h));
+  KSH_HIP(hipMemcpyAsync(h, ctl, first_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+  KSH_HIP(hipStreamSynchronize(ctx->stream));
+  if (h[3] != 0) return fail(KSH_INTERNAL, "ksh_kss_color_classes: a workgroup's class table was full");
+  const int64_t n = h[2];
+  if (h[1] != 0 || n > capacity) {
+    *n_classes = capacity + 1;
+    return fail(KSH_FAILED_PRECONDITION, "ksh_kss_color_classes: the chosen columns have more than capacity = %lld "
+                                         "colour classes: call again with a larger capacity", (long long)capacity);
+  }
+  std::vector<std::array<uint64_t, 3>> got(static_cast<size_t>(n));
+  const int64_t n_first = std::min(n, first);
+  for (int64_t c = 0; c < n_first; c++)
+    got[size_t(c)] = {uint64_t(h[kCtlWords + 3 * c]), uint64_t(h[kCtlWords + 3 * c + 1]),
+                      uint64_t(h[kCtlWords + 3 * c + 2])};
+  if (n > n_first) {  // a table of more than kFirstCopy classes: the rest, straight into the vector
+    KSH_HIP(hipMemcpyAsync(got.data() + n_first, ctl + kCtlWords + 3 * n_first, size_t(n - n_first) * 24,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    KSH_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  // ascending by (r1, r0) as one 128-bit integer.  On the host on purpose: the table is small and the call has
+  // synchronised.
+  std::sort(got.begin(), got.end(), [](const std::array<uint64_t, 3>& a, const std::array<uint64_t, 3>& b) {
+    return a[1] != b[1] ? a[1] < b[1] : a[0] < b[0];
+  });
+  for (int64_t c = 0; c < n; c++) {
+    rows[2 * c] = got[size_t(c)][0];
+    rows[2 * c + 1] = got[size_t(c)][1];
+    counts[c] = int64_t(got[size_t(c)][2]);
+  }
+  *n_classes = n;
+  return KSH_OK;
+}

@@ -211,7 +211,8 @@ struct NodeRef {
   int64_t n;
 };
 // d_flags: int[4] -- [0] the join searched an oversize slice in global memory, [1] ksh_kss_pair_counts (or
-// ksh_kss_select_*, ksh_select.hip) cut a bucket by key range, [2] one of its workgroups flushed its counters before its last tile.
+// ksh_kss_select_*, ksh_select.hip) cut a bucket by key range, [2] one of its workgroups flushed its counters before its last tile,
+// [3] a workgroup of ksh_kss_color_classes (ksh_classes.hip) spilled its class table before its last tile.
 struct IndexShape {
   ksh_ctx* ctx;
   ksh_geom g;

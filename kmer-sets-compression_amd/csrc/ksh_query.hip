@@ -532,11 +532,12 @@ int ksh_kss_index_routes(const ksh_kss_index* idx, uint32_t* bits) {
   if (!idx || !bits) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
   ksh_ctx* ctx = idx->ctx;
   KSH_HIP(hipSetDevice(ctx->device));
-  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, idx->d_flags, 12, hipMemcpyDeviceToHost, ctx->stream));
+  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, idx->d_flags, 16, hipMemcpyDeviceToHost, ctx->stream));
   KSH_HIP(hipStreamSynchronize(ctx->stream));
   const int* flags = reinterpret_cast<const int*>(ctx->h_pinned);
   *bits = idx->routes | (flags[0] ? uint32_t(KSH_QROUTE_OVERSIZE) : 0u) |
-          (flags[1] ? uint32_t(KSH_QROUTE_PAIR_SPLIT) : 0u) | (flags[2] ? uint32_t(KSH_QROUTE_PAIR_FLUSH) : 0u);
+          (flags[1] ? uint32_t(KSH_QROUTE_PAIR_SPLIT) : 0u) | (flags[2] ? uint32_t(KSH_QROUTE_PAIR_FLUSH) : 0u) |
+          (flags[3] ? uint32_t(KSH_QROUTE_CLASS_SPILL) : 0u);
   return KSH_OK;
 }
 

@@ -1,5 +1,5 @@
-// The tile walk over a KmerSetSet index that ksh_kss_pair_counts (ksh_paircounts.hip) and ksh_kss_select_*
-// (ksh_select.hip) share.  gfx950 only.
+// The tile walk over a KmerSetSet index that ksh_kss_pair_counts (ksh_paircounts.hip), ksh_kss_select_*
+// (ksh_select.hip) and ksh_kss_color_classes (ksh_classes.hip) share.  gfx950 only.
 //
 // A workgroup of kThreads walks one bucket at a time.  A bucket whose entries (all nodes together) fit a tile is
 // one tile; otherwise the workgroup walks the bucket's key range left to right and cuts it by key: every tile is
@@ -7,6 +7,12 @@
 // A tile's distinct keys and their rows over the chosen columns (the OR of proj[j] over the nodes j that hold the
 // key) are formed in an LDS hash table: atomicCAS on the key, atomicOr on the row.  What is done with the occupied
 // slots is the caller's; it leaves every slot empty (kEmpty, zero row) for the next tile.
+//
+// Callers rely on the barriers inside the walk: pc_bucket_begin and pc_tile_cut each pass at least one
+// __syncthreads() in every thread, on every path (pc_block_sum, pc_prefix), and pc_tile_fill one between its two
+// loops.  k_color_classes has thread 0 write an LDS flag ahead of pc_bucket_begin that all threads read after it,
+// and reads its table's occupancy behind pc_tile_cut.  An edit that takes a barrier out of one of the three must
+// give those callers one of their own.
 #ifndef KSH_ROWTILE_H_
 #define KSH_ROWTILE_H_
 
@@ -231,6 +237,21 @@ __device__ __forceinline__ void pc_tile_fill(const NodeRef* __restrict__ nodes, 
 }
 
 }  // namespace pc
+
+// Pinned words for the read-back of a call's results (the pair batch's buffer: every call that uses it has
+// synchronised the stream before it returns, so none finds another's words in use).
+inline int pinned_words(ksh_ctx* ctx, size_t n, int64_t** out) {
+  if (ctx->h_batch_count < n) {
+    if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+    ctx->h_batch = nullptr;
+    ctx->h_batch_count = 0;
+    if (hipHostMalloc(reinterpret_cast<void**>(&ctx->h_batch), n * sizeof(int64_t)) != hipSuccess)
+      return fail(KSH_INTERNAL, "hipHostMalloc failed");
+    ctx->h_batch_count = n;
+  }
+  *out = ctx->h_batch;
+  return KSH_OK;
+}
 
 // proj[2 j], proj[2 j + 1] = anc[j] projected onto the n_cols columns of `cols`, for every node j, enqueued on the
 // context's stream (ksh_paircounts.hip).  cols travel as a kernel argument: nothing of the caller's is read after

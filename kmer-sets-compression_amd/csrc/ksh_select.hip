@@ -268,21 +268,6 @@ static int resolve_request(const ksh_kss_selection* sel, const IndexShape& x, Co
   return KSH_OK;
 }
 
-// Pinned words for the read-back of a call's results (the pair batch's buffer: both calls have synchronised the
-// stream before they return, so neither finds the other's words in use).
-static int pinned_words(ksh_ctx* ctx, size_t n, int64_t** out) {
-  if (ctx->h_batch_count < n) {
-    if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
-    ctx->h_batch = nullptr;
-    ctx->h_batch_count = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&ctx->h_batch), n * sizeof(int64_t)) != hipSuccess)
-      return fail(KSH_INTERNAL, "hipHostMalloc failed");
-    ctx->h_batch_count = n;
-  }
-  *out = ctx->h_batch;
-  return KSH_OK;
-}
-
 // The walk both calls start with: route bits cleared, results zeroed, proj formed.
 static int begin_pass(ksh_kss_index* idx, const IndexShape& x, const ColList& list, int n_cols, PoolBuf* proj,
                       PoolBuf* acc) {

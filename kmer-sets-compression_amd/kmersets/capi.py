@@ -195,6 +195,8 @@ def lib():
         "ksh_kss_pair_counts": (C.c_int, [C.POINTER(i32), i32, vp, i64, vp, C.POINTER(i64)]),
         "ksh_kss_select_count": (C.c_int, [C.POINTER(Selection), vp, vp, C.POINTER(i64), C.POINTER(i64)]),
         "ksh_kss_select_keys": (C.c_int, [C.POINTER(Selection), vp, vp, i64, vp]),
+        "ksh_kss_color_classes": (C.c_int, [C.POINTER(i32), i32, vp, i64, C.POINTER(C.c_uint64), C.POINTER(i64),
+                                            C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1001,7 +1003,7 @@ class DeviceKmerSetSet:
 
 
 QROUTE_SEARCH, QROUTE_JOIN, QROUTE_OVERSIZE, QROUTE_CHUNKED, QROUTE_SEQ_PASSES = 1, 2, 4, 8, 16
-QROUTE_PAIR_SPLIT, QROUTE_PAIR_FLUSH = 32, 64
+QROUTE_PAIR_SPLIT, QROUTE_PAIR_FLUSH, QROUTE_CLASS_SPILL = 32, 64, 128
 
 
 class KssIndex:
@@ -1194,6 +1196,47 @@ class KssIndex:
         """np.int64[n_cols + 1]: element m is the number of distinct k-mers of the whole structure that exactly m of
         the sets Get(cols[a]) hold (element 0: those that only nodes outside cols hold)."""
         return self.select_count(cols, offsets=False, size=False, spectrum=True)[2]
+
+    def color_classes(self, cols=None, capacity=None):
+        """ksh_kss_color_classes: (rows, counts) -- rows np.uint64[n, 2], one distinct membership pattern over the
+        columns per line (bit a % 64 of rows[c, a // 64]: the class's k-mers are in Get(cols[a])), counts np.int64[n]
+        the distinct k-mers of the structure with exactly that pattern, ascending by (rows[c, 1], rows[c, 0]).  Row
+        zero counts the k-mers that only nodes outside cols hold.  cols: up to 128 distinct node ids (None: all
+        nodes).  capacity None: room for min(2^n_cols, 2^16) classes, times 4 for as long as the call answers that
+        there are more, up to min(2^n_cols, 2^24), where the refusal is raised; a given capacity is tried once."""
+        import torch
+
+        with torch.cuda.stream(self.ctx.stream):   # (results are read on the context's stream, not torch's current)
+            h = self._handle()
+            if cols is None:
+                n, ids, keep = self.n_nodes, None, None
+            else:
+                keep = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+                n = int(keep.size)
+                ids = (keep if n else np.zeros(1, dtype=np.int32)).ctypes.data_as(C.POINTER(C.c_int32))  # (never NULL)
+            top = 1 << min(max(n, 0), 24)  # min(2^n_cols, 2^24)
+            cap = min(top, 1 << 16) if capacity is None else int(capacity)
+            while True:
+                room = min(max(cap, 1), 1 << 24)  # (what the call refuses is never written)
+                rows = np.zeros((room, 2), dtype=np.uint64)
+                counts = np.zeros(room, dtype=np.int64)
+                got = C.c_int64()
+                rc = lib().ksh_kss_color_classes(ids, n if cols is not None else 0, h, cap,
+                                                 rows.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(got))
+                if rc == KSH_FAILED_PRECONDITION and got.value == cap + 1 and capacity is None and cap < top:
+                    cap = min(4 * cap, top)
+                    continue
+                check(rc)
+                del keep
+                return rows[:got.value].copy(), counts[:got.value].copy()
+
+    @staticmethod
+    def class_matrix(rows, n_cols):
+        """bool[n, n_cols] of the rows color_classes returned: element [c, a] is bit a of class c."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+        bits = np.unpackbits(rows.view(np.uint8).reshape(rows.shape[0], 16), axis=1, bitorder="little")
+        return bits[:, :int(n_cols)].astype(bool)
 
     def jaccard(self, cols=None):
         """Exact Jaccard similarities c_ab / (c_aa + c_bb - c_ab) of the sets Get(cols[a]), a float64 numpy array

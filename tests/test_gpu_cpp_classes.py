@@ -1,0 +1,24 @@
+"""The C++17 host mirror's KmerSetSetIndex::ColorClasses (kmer-sets-compression_amd/cpp/core/kmer_set_set.h), driven
+by cpp/test/test_classes.cc: on one small family the class table of the inputs equals the one counted on the host from
+the mirror's own Get(i), its sums are Spectrum and PairCounts, and a capacity that is too small is refused."""
+import os
+import subprocess
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CPP = os.path.join(ROOT, "kmer-sets-compression_amd", "cpp")
+
+
+def test_cpp_classes_mirror(gpu):
+    from kmersets import capi
+
+    capi.build()
+    subprocess.check_call(["make", "-C", CPP, "-s", "build/test_classes"])
+    out = subprocess.run([os.path.join(CPP, "build", "test_classes")], capture_output=True, text=True, timeout=600)
+    print(out.stdout)
+    print(out.stderr)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "0 failed" in out.stdout
