@@ -303,7 +303,9 @@ int ksh_spss_decode_write(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* 
  * (lib/core/kmer_set_compact.h:62-87 over WriteLines / ReadLines, lib/core/io.h:20-126): one
  * string over ACGT per line, every line closed by '\n'; the reference spells / parses it base
  * by base on the host (ToStrings :290-336, the private constructor :206-266).
- * to_text: d_text receives exactly n_bases + n_strings bytes.
+ * to_text: d_text receives exactly n_bases + n_strings bytes and needs no alignment; a view whose
+ * string lengths do not sum to n_bases is KSH_INVALID_ARGUMENT, refused before anything is written.
+ * from_text: d_text needs no alignment either.
  * from_text: plan counts the lines and bases of n_bytes of text in device memory (a last line
  * without '\n' counts); the caller allocates ceil(n_bases / 32) words and n_strings lengths;
  * write fills them (ksh_spss_view layout).  A byte other than A, C, G, T, '\n' or a line

@@ -222,18 +222,19 @@ int ksh_spss_to_text(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, ch
   hipLaunchKernelGGL(k_text_str_bases, dim3(blocks_of(s->n_strings, 256)), dim3(256), 0, st, s->d_lens,
                      s->n_strings, g->k, str_start);
   KSH_TRY(scan_exclusive_i64(ctx, str_start, str_start, s->n_strings, str_start + s->n_strings));
+  // the strings must tile the base stream exactly; this is known before anything is indexed by a string
+  // end: with lengths that sum to more than n_bases, k_text_mark_ends would set bits past end_bits
+  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, str_start + s->n_strings, 8, hipMemcpyDeviceToHost, st));
+  KSH_HIP(hipStreamSynchronize(st));
+  if (ctx->h_pinned[0] != s->n_bases)
+    return fail(KSH_INVALID_ARGUMENT, "sum of string lengths (%lld) != n_bases (%lld)",
+                static_cast<long long>(ctx->h_pinned[0]), static_cast<long long>(s->n_bases));
   KSH_HIP(hipMemsetAsync(end_bits, 0, size_t(n_chunks) * 8, st));
   hipLaunchKernelGGL(k_text_mark_ends, dim3(blocks_of(s->n_strings, 256)), dim3(256), 0, st, str_start,
                      s->n_strings, end_bits);
   hipLaunchKernelGGL(k_text_popc, dim3(blocks_of(n_chunks, 256)), dim3(256), 0, st, end_bits, n_chunks,
                      ends_before);
   KSH_TRY(scan_exclusive_i64(ctx, ends_before, ends_before, n_chunks, ends_before + n_chunks));
-  // the strings must tile the base stream exactly
-  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, str_start + s->n_strings, 8, hipMemcpyDeviceToHost, st));
-  KSH_HIP(hipStreamSynchronize(st));
-  if (ctx->h_pinned[0] != s->n_bases)
-    return fail(KSH_INVALID_ARGUMENT, "sum of string lengths (%lld) != n_bases (%lld)",
-                static_cast<long long>(ctx->h_pinned[0]), static_cast<long long>(s->n_bases));
   hipLaunchKernelGGL(k_to_text, dim3(blocks_of(n_chunks, kTextThreads)), dim3(kTextThreads), 0, st, s->d_words,
                      s->n_bases, end_bits, ends_before, reinterpret_cast<unsigned char*>(d_text));
   KSH_HIP(hipGetLastError());
