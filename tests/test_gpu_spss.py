@@ -5,6 +5,7 @@ Bit-exact: the strings must equal the oracle's, in order."""
 import numpy as np
 import pytest
 
+import bucket_sort_cases as bsc
 import oracle_lib as ol
 from kmersets import capi, synth
 
@@ -250,6 +251,9 @@ def test_decode_oversize_buckets(ctx, geom):
     lines must still collapse."""
     k, n, kb = geom
     kmers = synth.random_read_kmers(k, 60000, seed=31 + k, canonical=True)
+    # (canonical k-mers crowd the low buckets: the fullest holds well over a quarter of them)
+    assert bsc.largest_bucket(kmers, k, n) > bsc.k_cap(kb)
+    assert "partition" in bsc.bucket_branches(kmers[kmers >> np.uint64(2 * k - n) == 0], 2 * k - n, kb)
     oset = ol.Set.from_kmers(k, n, kb, kmers)
     strings = oset.spss()
     strings = strings + strings[:50]          # duplicates
