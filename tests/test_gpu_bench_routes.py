@@ -16,6 +16,7 @@ import pytest
 
 import oracle_lib as ol
 from kmersets import capi, synth
+from probe_cases import RC1_CAP, rc_shape, records_per_group
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -88,30 +89,13 @@ def test_bench_geometry_two_level_jumping(ctx):
                                     "jump_two_level", "emit_logs"}, {"rank_stamped"})
 
 
-# Rc1Cfg<KeyT>::kCap (csrc/ksh_encode.hip): (kRc1LdsBytes - kRc1SlicesMax * 4) / entry bytes, a multiple of 8;
-# an entry is one 8-byte word for 2- and 4-byte keys, key + 6 bytes for 8-byte keys
-RC1_CAP = {2: (81408 - 4096 * 4) // 8 & ~7, 4: (81408 - 4096 * 4) // 8 & ~7, 8: (81408 - 4096 * 4) // 14 & ~7}
-
-
-def rc_shape(n, nbits, kb):
-    """(per_group, threads route, rc1_cap) as the encode plan computes them for a staged probe without half groups."""
-    per_group = n >> nbits
-    threads = "rc_1024" if per_group > 4096 else "rc_512" if per_group > 1024 else "rc_256" if per_group > 256 else "rc_64"
-    return per_group, threads, min(RC1_CAP[kb], (per_group * 4 // 3 + 263) & ~7)
+# (RC1_CAP, rc_shape and records_per_group live in tests/probe_cases.py, beside the model of the probe that uses them)
 
 
 def test_rc1_cap_arithmetic():
     assert RC1_CAP == {2: 8128, 4: 8128, 8: 4640}
     assert rc_shape(1_400_000, 8, 4) == (5468, "rc_1024", 7552)
     assert rc_shape(1_100_000, 8, 8)[1:] == ("rc_1024", 4640)
-
-
-def records_per_group(kmers, k, nbits):
-    """How many rc records each group gets: x's record is rc(x), grouped by the nbits below its top base
-    (csrc/ksh_encode.hip, k_rc_hist)."""
-    rx = synth.revcomp(kmers, k)
-    grp = (rx >> np.uint64(2 * k - 2 - nbits)) & np.uint64((1 << nbits) - 1)
-    return np.bincount(grp.astype(np.int64), minlength=1 << nbits)
 
 
 @pytest.mark.parametrize("k,n,kb,size,threads,marks", [
@@ -146,7 +130,7 @@ def stream_parts(kmers, k, chunk=2048, stream_max=4096):
     """Parts beyond the first that k_tgt_split makes (tests/test_model_probe_partition.py, cuts_of): a window of
     `chunk` k-mers, cut where the (K-1)-base prefix changes, streams the k-mers whose suffix lies in its prefix
     range, and a stream longer than stream_max is cut into ceil(stream / stream_max) parts."""
-    from test_model_probe_partition import cuts_of
+    from probe_cases import cuts_of
 
     _, v = cuts_of(kmers, k, chunk)
     v = np.array(v, dtype=np.uint64)
