@@ -731,8 +731,6 @@ struct DecodeState {
   int64_t* coarse;      // wide route only: [2^kCoarseBits + 1] coarse bucket offsets, plan -> write
 };
 
-inline size_t a256(size_t x) { return (x + 255) & ~size_t(255); }
-
 int check_spss(const ksh_spss_view* s) {
   if (!s) return fail(KSH_INVALID_ARGUMENT, "spss is NULL");
   if (s->n_strings < 0 || s->n_bases < 0) return fail(KSH_INVALID_ARGUMENT, "negative spss size");
@@ -751,19 +749,24 @@ void decode_geometry(const ksh_spss_view* s, int64_t* n_words, int64_t* n_end_wo
   *words_per_group = (*n_words + g - 1) / g;
 }
 
-// nb: the buckets the counting pass works on (2^kCoarseBits on the wide route)
-void decode_carve(ksh_ctx* ctx, int64_t groups, int64_t nb, int64_t n_end_words, int64_t n_strings,
-                  DecodeState* st) {
-  char* at = ctx->slot[kSlotDecode];
-  st->hist = reinterpret_cast<uint32_t*>(at);
-  at += a256(size_t(groups) * nb * 4);
-  st->end_bits = reinterpret_cast<unsigned long long*>(at);
-  at += a256(size_t(n_end_words) * 8);
-  st->str_start = reinterpret_cast<int64_t*>(at);
-  at += a256(size_t(n_strings + 1) * 8);
-  st->totals = reinterpret_cast<int64_t*>(at);
-  at += a256(size_t(nb + 2) * 8);
-  st->coarse = reinterpret_cast<int64_t*>(at);
+// The decode's arrays in slot kSlotDecode.  nb: the buckets the counting pass works on (2^kCoarseBits on the wide
+// route, which also keeps their offsets).
+struct DecodeShape {
+  int64_t groups, nb, n_end_words, n_strings;
+  bool wide;
+};
+void decode_layout(Carver& c, const DecodeShape& d, DecodeState* st) {
+  st->hist = c.take<uint32_t>(size_t(d.groups) * d.nb);
+  st->end_bits = c.take<unsigned long long>(size_t(d.n_end_words));
+  st->str_start = c.take<int64_t>(size_t(d.n_strings + 1));
+  st->totals = c.take<int64_t>(size_t(d.nb + 2));
+  st->coarse = d.wide ? c.take<int64_t>(size_t(d.nb + 1)) : nullptr;
+}
+// (the plan reserves what the list measures; a write finds the slot as its plan left it)
+int decode_carve(ksh_ctx* ctx, const DecodeShape& d, DecodeState* st) {
+  if (!layout_bind(ctx->slot[kSlotDecode], ctx->slot_bytes[kSlotDecode], [&](Carver& c) { decode_layout(c, d, st); }))
+    return fail(KSH_INTERNAL, "scratch arena too small");
+  return KSH_OK;
 }
 
 // ---- the wide route: N > 14 ------------------------------------------------------------------
@@ -850,14 +853,11 @@ int decode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int c
   const int kbw = wide ? 2 * g->k - kCoarseBits : key_bits(g);
   int64_t n_words, n_end_words, groups, wpg;
   decode_geometry(s, &n_words, &n_end_words, &groups, &wpg);
-  const size_t bytes = a256(size_t(groups) * nbw * 4) + a256(size_t(n_end_words) * 8) +
-                       a256(size_t(s->n_strings + 1) * 8) + a256(size_t(nbw + 2) * 8) +
-                       (wide ? a256(size_t(nbw + 1) * 8) : 0);
-  KSH_TRY(slot_reserve(ctx, kSlotDecode, bytes));
-  KSH_TRY(arena_reserve(ctx, size_t(s->n_strings / 256 + 4096) * 8 + (1u << 16)));
-  arena_reset(ctx);
+  const DecodeShape shape{groups, nbw, n_end_words, s->n_strings, wide};
   DecodeState st;
-  decode_carve(ctx, groups, nbw, n_end_words, s->n_strings, &st);
+  KSH_TRY(slot_layout(ctx, kSlotDecode, [&](Carver& c) { decode_layout(c, shape, &st); }));
+  KSH_TRY(arena_reserve(ctx, scan_scratch_bytes(s->n_strings)));
+  arena_reset(ctx);
   int64_t* offw = wide ? st.coarse : d_offsets;
 
   const unsigned sb = unsigned((s->n_strings + 255) / 256);
@@ -972,11 +972,10 @@ int scatter_sort(ksh_ctx* ctx, const ksh_spss_view* s, const DecodeState& st, in
       scratch = static_cast<KeyT*>(ptr);
     }
   }
-  arena_reset(ctx);
-  KSH_TRY(arena_reserve(ctx, 2 * a256(size_t(nb + 1) * 8) + (1u << 16)));
-  *new_off = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb + 1) * 8));
-  *below = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb + 1) * 8));
-  if (!*new_off || !*below) return fail(KSH_INTERNAL, "scratch arena too small");
+  KSH_TRY(arena_layout(ctx, 1u << 16, [&](Carver& c) {  // (+ the block sums of the scans over them)
+    *new_off = c.take<int64_t>(size_t(nb + 1));
+    *below = c.take<int64_t>(size_t(nb + 1));
+  }));
   {
     // (more than the 64 KB a kernel gets without asking)
     const uint32_t bit = 8u << (sizeof(KeyT) == 2 ? 0 : sizeof(KeyT) == 4 ? 1 : 2);
@@ -1002,7 +1001,7 @@ int decode_write_wide(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, i
   int64_t n_words, n_end_words, groups, wpg;
   decode_geometry(s, &n_words, &n_end_words, &groups, &wpg);
   DecodeState st;
-  decode_carve(ctx, groups, nbc, n_end_words, s->n_strings, &st);
+  KSH_TRY(decode_carve(ctx, DecodeShape{groups, nbc, n_end_words, s->n_strings, true}, &st));
   KeyT* keys = static_cast<KeyT*>(d_keys);
   constexpr bool in_place = sizeof(CT) == sizeof(KeyT);
   CT* comp = reinterpret_cast<CT*>(d_keys);
@@ -1071,7 +1070,7 @@ int decode_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int 
   int64_t n_words, n_end_words, groups, wpg;
   decode_geometry(s, &n_words, &n_end_words, &groups, &wpg);
   DecodeState st;
-  decode_carve(ctx, groups, nb, n_end_words, s->n_strings, &st);
+  KSH_TRY(decode_carve(ctx, DecodeShape{groups, nb, n_end_words, s->n_strings, false}, &st));
   KeyT* keys = static_cast<KeyT*>(d_keys);
   int64_t *new_off = nullptr, *below = nullptr;
   KSH_TRY(scatter_sort<KeyT>(ctx, s, st, g->k, g->n_bucket_bits, key_bits(g), canonical_flag, d_offsets, keys,

@@ -3550,6 +3550,8 @@ struct EncPlan {
   uint32_t* fine = nullptr;
   int fine_bits = 0;
   uint32_t* coarse = nullptr;  // DevSet::coarse (sets of at least four k-mers per bucket)
+  // bytes of the arrays that other stages borrow, as the slot's layout took them (the KSH_BOUNDs compare with these)
+  size_t nbr_bytes = 0, link_bytes = 0, info_bytes = 0, ori_bytes = 0;
   // unitig level (own allocation)
   char* ublock = nullptr;
   uint32_t *u_head = nullptr, *u_first = nullptr, *u_last = nullptr, *u_len = nullptr,
@@ -3578,8 +3580,6 @@ struct EncPlan {
   bool written = false;         // a write has served it
   bool ambiguous = false;       // it replaced an unwritten plan of its own kind (claim_nameless)
 };
-
-inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
 // Host-side statement of what a kernel's indexing assumes about the scratch it borrows (carved arrays
 // that change hands between stages, LDS byte counts, packed 16-bit fields): checked before the launch.
@@ -3643,13 +3643,6 @@ inline int64_t l2_threshold() {
 // buy is the idle time between one encode's kernels and behind its host round trips.)
 inline unsigned nblk(int64_t n) { return unsigned(std::max<int64_t>(1, (n + 255) / 256)); }
 
-template <typename T>
-T* carve(char*& at, size_t count) {
-  T* p = reinterpret_cast<T*>(at);
-  at += al(count * sizeof(T));
-  return p;
-}
-
 void free_plan(ksh_ctx* ctx) {
   EncPlan* p = static_cast<EncPlan*>(ctx->enc_state);
   if (!p) return;
@@ -3677,19 +3670,78 @@ static int enc_fine_bits(const ksh_geom* g, int64_t n) {
   while (fine_bits < 13 && fine_bits + 2 < key_bits(g) && (int64_t(3) << fine_bits) < 2 * (n / nb + 1)) fine_bits++;
   return fine_bits;
 }
-static size_t enc_slot_bytes(const ksh_geom* g, int64_t n) {
+// The k-mer level arrays of an encode of n k-mers, in slot kSlotEncode.  Its measure must not decrease as n grows (a lane
+// reserves once, at its largest n): every count is non-decreasing in n, what only some sets use (coarse) counts for all.
+static void enc_slot_layout(Carver& c, EncPlan* p, const ksh_geom* g, int64_t n) {
   const int64_t nb = n_buckets(g);
   const int fine_bits = enc_fine_bits(g, n);
-  const size_t fine_entries = fine_bits >= 2 ? (size_t(nb) << fine_bits) + 1 : 0;
-  return 2 * al(size_t(2 * n) * 4) + al(size_t(2 * n) * 8) + 5 * al(size_t(n) * 4) + 2 * al(size_t(n)) +
-         2 * al(size_t(n) * 8) + al(fine_entries * 4) + al(size_t((n >> kCoarseShift) + 2) * 4) +
-         al(sizeof(EncCtl) + size_t(2 * nb) * 4) + 4096;
+  p->nbr = c.take<uint32_t>(size_t(2 * n), &p->nbr_bytes);
+  p->link = c.take<uint32_t>(size_t(2 * n), &p->link_bytes);
+  p->info = c.take<unsigned long long>(size_t(2 * n), &p->info_bytes);
+  p->head = c.take<uint32_t>(size_t(n));
+  p->pos = c.take<uint32_t>(size_t(n));
+  p->hlen = c.take<uint32_t>(size_t(n));
+  p->hlast = c.take<uint32_t>(size_t(n));
+  p->uid = c.take<uint32_t>(size_t(n));
+  p->ori = c.take<uint8_t>(size_t(n), &p->ori_bytes);
+  p->hcls = c.take<uint8_t>(size_t(n));
+  p->c01 = c.take<int64_t>(size_t(2 * n));  // two arrays of n, one block: later the place records
+  p->c23 = p->c01 ? p->c01 + n : nullptr;
+  c.pad(2 * round256(size_t(n) * 8) - round256(size_t(2 * n) * 8));  // (the two halves used to be counted as two arrays)
+  p->fine = fine_bits >= 2 ? c.take<uint32_t>((size_t(nb) << fine_bits) + 1) : nullptr;
+  p->coarse = c.take_if<uint32_t>(n >= 4 * nb, size_t((n >> kCoarseShift) + 2));
+  p->ctl = reinterpret_cast<EncCtl*>(c.take<char>(sizeof(EncCtl) + size_t(2 * nb) * 4));  // + k_rc_scatter_l2's cursors
+  c.pad(4096);  // spare of the hand-written sum
 }
+static size_t enc_slot_bytes(const ksh_geom* g, int64_t n) {
+  EncPlan measured;
+  return layout_bytes([&](Carver& c) { enc_slot_layout(c, &measured, g, n); });
+}
+// Upper bound of what a plan takes from the arena (which of the pieces it takes depends on routes chosen later).
 static size_t enc_arena_bytes(const ksh_geom* g, int64_t n) {
-  const int64_t nb = n_buckets(g);
-  return size_t(n / 256 + 4096) * 8 * 2 + (1u << 16) + size_t(n / kHeadSpan + 64) * 8 +
-         (nb <= (1 << 14) ? size_t(kRcRowsMax) * 2 * nb * 4 + size_t(2 * nb + 1) * 16 + size_t(2 * nb) * 280 + 8192 : 0);
+  const size_t nb = size_t(n_buckets(g));
+  // the scans' block sums: two scans' worth of sums (cover_stage runs two back to back), one alignment allowance
+  size_t bytes = 2 * scan_scratch_bytes(n) - (1u << 16);
+  bytes += size_t(n / kHeadSpan + 64) * 8;  // end_before: int64[n_hblocks + 1]
+  if (nb <= (size_t(1) << 14)) {            // the staged probe, at most 2 nb groups (KSH_RC_GROUPS=half)
+    bytes += size_t(kRcRowsMax) * 2 * nb * 4;  // hist: u32[rows * ng]
+    bytes += (2 * nb + 1) * 16;                // totals and goff: int64[ng + 1] each
+    bytes += 2 * nb * 280;                     // pb: int64[ng * 2 * kRcSegs], pb0: int64[ng * 2], 8 bytes a group spare
+    bytes += 8192;                             // the five blocks' alignment; cuts, for a set too small to lend them `info`
+  }
+  return bytes;
 }
+// The arrays of cover_stage over n_u unitigs: part of the encode's unitig block and of the cover plan's block.
+static void unitig_stage_layout(Carver& c, EncPlan* p, size_t n_u) {
+  p->u_len = c.take<uint32_t>(n_u);
+  p->u_sid = c.take<uint32_t>(n_u);
+  p->u_koff = c.take<uint32_t>(n_u);
+  p->lens = c.take<uint32_t>(n_u);
+  p->sc_nodes = c.take<uint32_t>(n_u);
+  p->sc_parent = c.take<uint32_t>(n_u);
+  p->sc_rank = c.take<uint32_t>(n_u);
+  p->edges = c.take<uint32_t>(8 * n_u);
+  p->mate = c.take<uint32_t>(2 * n_u);
+  p->best_w = c.take<uint32_t>(2 * n_u);
+  p->best_prio = c.take<unsigned long long>(2 * n_u);
+  p->visited = c.take<uint8_t>(n_u);
+  p->scls = c.take<uint8_t>(n_u);
+  p->u_flip = c.take<uint8_t>(n_u);
+  p->s_nk = c.take<int64_t>(n_u + 1);
+  p->sc01 = c.take<int64_t>(n_u + 1);
+  p->sc2 = c.take<int64_t>(n_u + 1);
+  p->str_start = c.take<int64_t>(n_u + 1);
+}
+// The encode's unitig block (from the pool: the byte count decides its size class).
+static void enc_unitig_layout(Carver& c, EncPlan* p, size_t n_u) {
+  p->u_head = c.take<uint32_t>(n_u);
+  p->u_first = c.take<uint32_t>(n_u);
+  p->u_last = c.take<uint32_t>(n_u);
+  unitig_stage_layout(c, p, n_u);
+  c.pad(3 * round256(n_u * 4));  // three u32[n_u] arrays that no kernel uses any more, still counted
+  c.pad(4096);                   // spare of the hand-written sum
+}
+
 size_t encode_scratch_bytes(const ksh_geom* g, int64_t n) {
   const size_t slot = enc_slot_bytes(g, n), arena = enc_arena_bytes(g, n);
   return slot + (slot >> 3) + arena + (arena >> 2) + (size_t(2) << 20);  // (with slot_reserve's and arena_reserve's spare)
@@ -3794,25 +3846,9 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
   const int64_t nb = n_buckets(g);
   const int fine_bits = enc_fine_bits(g, n);
   const bool use_fine = fine_bits >= 2;
-  const size_t fine_entries = use_fine ? (size_t(nb) << fine_bits) + 1 : 0;
   KSH_TRY(encode_reserve(ctx, g, n));
   arena_reset(ctx);
-  char* at = ctx->slot[kSlotEncode];
-  p->nbr = carve<uint32_t>(at, size_t(2 * n));
-  p->link = carve<uint32_t>(at, size_t(2 * n));
-  p->info = carve<unsigned long long>(at, size_t(2 * n));
-  p->head = carve<uint32_t>(at, size_t(n));
-  p->pos = carve<uint32_t>(at, size_t(n));
-  p->hlen = carve<uint32_t>(at, size_t(n));
-  p->hlast = carve<uint32_t>(at, size_t(n));
-  p->uid = carve<uint32_t>(at, size_t(n));
-  p->ori = carve<uint8_t>(at, size_t(n));
-  p->hcls = carve<uint8_t>(at, size_t(n));
-  p->c01 = carve<int64_t>(at, size_t(2 * n));  // two arrays of n, one block: later the place records
-  p->c23 = p->c01 + n;
-  p->fine = use_fine ? carve<uint32_t>(at, fine_entries) : nullptr;
-  p->coarse = n >= 4 * nb ? carve<uint32_t>(at, size_t((n >> kCoarseShift) + 2)) : nullptr;
-  p->ctl = reinterpret_cast<EncCtl*>(carve<char>(at, sizeof(EncCtl) + size_t(2 * nb) * 4));
+  KSH_BOUND(layout_bind(ctx->slot[kSlotEncode], ctx->slot_bytes[kSlotEncode], [&](Carver& c) { enc_slot_layout(c, p, g, n); }));
   uint32_t* rc_cursor = reinterpret_cast<uint32_t*>(p->ctl + 1);  // k_rc_scatter_l2's per-group cursors: zeroed with the block
   EncCtl* ctl = p->ctl;
 
@@ -3849,7 +3885,7 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
       const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(kRcRowsMax, (n + 16383) / 16384));
       const int64_t per_row = ((n + rows - 1) / rows + 1023) / 1024 * 1024;
       KSH_BOUND(rows >= 1 && rows <= kRcRowsMax && rows * per_row >= n);  // k_rc_hist / k_rc_scatter_*: row r owns [r * per_row, ...)
-      KSH_BOUND(size_t(n) * sizeof(RcRecord<KeyT>) <= al(size_t(2 * n) * 8));  // the records live in `info`
+      KSH_BOUND(size_t(n) * sizeof(RcRecord<KeyT>) <= p->info_bytes);  // the records live in `info`
       static const bool one_level = [] {
         const char* e = getenv("KSH_RC_SCATTER");
         return e && std::string(e) == "direct";
@@ -3917,10 +3953,10 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
         RcRecord<KeyT>* tmp_rec = sizeof(RcRecord<KeyT>) == 8 ? rec + n : reinterpret_cast<RcRecord<KeyT>*>(p->nbr);
         uint16_t* tmp_g = reinterpret_cast<uint16_t*>(p->head);
         // intermediate records: u32 keys, the upper half of `info` (2n records of 8 bytes in 16n bytes);
-        // u64 keys, nbr + link (carved back to back: 2 x al(8n) >= 16n); group ids in `head` (2n <= 4n bytes)
-        KSH_BOUND(sizeof(RcRecord<KeyT>) == 8 ? size_t(2 * n) * sizeof(RcRecord<KeyT>) <= al(size_t(2 * n) * 8)
-                                    : reinterpret_cast<char*>(p->link) == reinterpret_cast<char*>(p->nbr) + al(size_t(2 * n) * 4) &&
-                                          size_t(n) * sizeof(RcRecord<KeyT>) <= 2 * al(size_t(2 * n) * 4));
+        // u64 keys, nbr + link (taken back to back: 8n bytes and more each); group ids in `head` (2n <= 4n bytes)
+        KSH_BOUND(sizeof(RcRecord<KeyT>) == 8 ? size_t(2 * n) * sizeof(RcRecord<KeyT>) <= p->info_bytes
+                                    : reinterpret_cast<char*>(p->link) == reinterpret_cast<char*>(p->nbr) + p->nbr_bytes &&
+                                          size_t(n) * sizeof(RcRecord<KeyT>) <= p->nbr_bytes + p->link_bytes);
         KSH_BOUND(gbits - kSgBits <= 8);  // k_rc_scatter_l2: two super-groups' groups in its 512 bins
         uint32_t* cursor = rc_cursor;     // (2^gbits zeroed words behind the control block)
         constexpr int kPer = sizeof(RcRecord<KeyT>) == 8 ? 4 : 2;
@@ -4007,8 +4043,8 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
         // cuts | (lo, hi) cut pairs of the windows, then of the parts | the parts' tasks
         // (a seventh of a byte per k-mer and 300 bytes: in the dead records, or for a set of a few k-mers in the arena)
         const size_t cut_bytes = size_t((n_chunks + 1) * kTgtBounds + (n_chunks + cap) * 2 * kTgtBounds) * 8 + size_t(cap) * sizeof(TgtTask);
-        int64_t* cuts = cut_bytes <= al(size_t(2 * n) * 8) ? reinterpret_cast<int64_t*>(p->info)
-                                                           : static_cast<int64_t*>(arena_alloc(ctx, cut_bytes));
+        int64_t* cuts = cut_bytes <= p->info_bytes ? reinterpret_cast<int64_t*>(p->info)
+                                                    : static_cast<int64_t*>(arena_alloc(ctx, cut_bytes));
         if (!cuts) return fail(KSH_INTERNAL, "scratch arena too small");
         int64_t* rec = cuts + (n_chunks + 1) * kTgtBounds;
         TgtTask* task = reinterpret_cast<TgtTask*>(rec + (n_chunks + cap) * 2 * kTgtBounds);
@@ -4025,7 +4061,7 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
         // the records are dead by now: the chunk bounds take their place
         const int64_t n_chunks = (n + kFwdChunk - 1) / kFwdChunk;
         int64_t* bounds = reinterpret_cast<int64_t*>(p->info);  // kFwdBounds * 8 bytes per 512 k-mers
-        KSH_BOUND(size_t(n_chunks + 1) * kFwdBounds * 8 <= al(size_t(2 * n) * 8));
+        KSH_BOUND(size_t(n_chunks + 1) * kFwdBounds * 8 <= p->info_bytes);
         hipLaunchKernelGGL((k_fwd_bounds<KeyT>), dim3(nblk((n_chunks + 1) * 10)), dim3(256), 0, st, set, n_chunks, bounds);
         // (measured and dropped, round 3: a Next window for twice the range, 6144 keys, still four workgroups per
         // CU: 3 % of the k-mers instead of 15 % fall back to probes in global memory, and the kernel takes
@@ -4064,7 +4100,7 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
   if (!end_before) return fail(KSH_INTERNAL, "scratch arena too small");
   uint32_t* ends = p->pos;  // (k_choose writes pos after the last kernel that reads the list)
   uint8_t* end_flags = p->ori;  // (the orientations are k_choose_ends' to fill later; a byte per eight k-mers until then)
-  KSH_BOUND(size_t(n_hblocks) * 256 <= al(size_t(n)));
+  KSH_BOUND(size_t(n_hblocks) * 256 <= p->ori_bytes);
   hipLaunchKernelGGL(k_end_counts, dim3(unsigned(n_hblocks)), dim3(256), 0, st, link, n, end_before, end_flags);
   KSH_TRY(scan_exclusive_i64(ctx, end_before, end_before, n_hblocks, end_before + n_hblocks));
   hipLaunchKernelGGL(k_end_fill, dim3(unsigned(n_hblocks)), dim3(256), 0, st, end_flags, n, end_before, ends, p->hcls);
@@ -4224,32 +4260,10 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
   p->n_u = n_u;
 
   // unitig-level block
-  const size_t ub = 10 * al(size_t(n_u) * 4) + al(size_t(8 * n_u) * 4) + 2 * al(size_t(2 * n_u) * 4) +
-                    al(size_t(2 * n_u) * 8) + 3 * al(size_t(n_u)) + 4 * al(size_t(n_u + 1) * 8) +
-                    3 * al(size_t(n_u) * 4) + 4096;
+  const auto unitig_block = [&](Carver& c) { enc_unitig_layout(c, p, size_t(n_u)); };
+  const size_t ub = layout_bytes(unitig_block);
   KSH_TRY(pool_alloc(ctx, ub, reinterpret_cast<void**>(&p->ublock)));
-  at = p->ublock;
-  p->u_head = carve<uint32_t>(at, size_t(n_u));
-  p->u_first = carve<uint32_t>(at, size_t(n_u));
-  p->u_last = carve<uint32_t>(at, size_t(n_u));
-  p->u_len = carve<uint32_t>(at, size_t(n_u));
-  p->u_sid = carve<uint32_t>(at, size_t(n_u));
-  p->u_koff = carve<uint32_t>(at, size_t(n_u));
-  p->lens = carve<uint32_t>(at, size_t(n_u));
-  p->sc_nodes = carve<uint32_t>(at, size_t(n_u));
-  p->sc_parent = carve<uint32_t>(at, size_t(n_u));
-  p->sc_rank = carve<uint32_t>(at, size_t(n_u));
-  p->edges = carve<uint32_t>(at, size_t(8 * n_u));
-  p->mate = carve<uint32_t>(at, size_t(2 * n_u));
-  p->best_w = carve<uint32_t>(at, size_t(2 * n_u));
-  p->best_prio = carve<unsigned long long>(at, size_t(2 * n_u));
-  p->visited = carve<uint8_t>(at, size_t(n_u));
-  p->scls = carve<uint8_t>(at, size_t(n_u));
-  p->u_flip = carve<uint8_t>(at, size_t(n_u));
-  p->s_nk = carve<int64_t>(at, size_t(n_u + 1));
-  p->sc01 = carve<int64_t>(at, size_t(n_u + 1));
-  p->sc2 = carve<int64_t>(at, size_t(n_u + 1));
-  p->str_start = carve<int64_t>(at, size_t(n_u + 1));
+  KSH_BOUND(layout_bind(p->ublock, ub, unitig_block));
   p->sc_used = &ctl->sc_used;
 
   hipLaunchKernelGGL(k_unitig_fill, dim3(unsigned(n_hblocks)), dim3(256), 0, st, p->hcls, b01, b23, n, n0,
@@ -4398,40 +4412,25 @@ int cover_plan(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* in, bool di
   const int n_tables = directed ? 2 : 1;
   uint64_t cap = 1;
   while (cap < uint64_t(4 * n)) cap <<= 1;
-  const size_t block = al(sizeof(EncCtl)) + al(kCoverErrCount * 8 + 8) + 7 * al(size_t(n) * 4) +
-                       al(size_t(8 * n) * 4) + 2 * al(size_t(2 * n) * 4) + al(size_t(2 * n) * 8) + 3 * al(size_t(n)) +
-                       5 * al(size_t(n + 1) * 8) + 2 * al(size_t(n) * 8) + al(n_tables * cap * 8) +
-                       al(n_tables * cap * 4) + 4096;
-  KSH_TRY(arena_reserve(ctx, size_t(n / 256 + 4096) * 8 * 2 + (1u << 16)));
+  unsigned long long *err = nullptr, *keys = nullptr;
+  uint64_t *first = nullptr, *last = nullptr;
+  uint32_t* vals = nullptr;
+  const auto cover_block = [&](Carver& c) {
+    p->ctl = reinterpret_cast<EncCtl*>(c.take<char>(sizeof(EncCtl)));
+    err = c.take<unsigned long long>(kCoverErrCount + 1);  // + the input's base total
+    unitig_stage_layout(c, p, size_t(n));
+    p->in_start = c.take<int64_t>(size_t(n + 1));
+    first = c.take<uint64_t>(size_t(n));
+    last = c.take<uint64_t>(size_t(n));
+    keys = c.take<unsigned long long>(n_tables * cap);
+    vals = c.take<uint32_t>(n_tables * cap);
+    c.pad(4096);  // spare of the hand-written sum
+  };
+  const size_t block = layout_bytes(cover_block);
+  KSH_TRY(arena_reserve(ctx, 2 * scan_scratch_bytes(n) - (1u << 16)));  // (as the encode: two scans' sums, one allowance)
   KSH_TRY(pool_alloc(ctx, block, reinterpret_cast<void**>(&p->ublock)));
-  char* at = p->ublock;
-  p->ctl = reinterpret_cast<EncCtl*>(carve<char>(at, sizeof(EncCtl)));
-  unsigned long long* err = carve<unsigned long long>(at, kCoverErrCount + 1);  // + the input's base total
+  KSH_BOUND(layout_bind(p->ublock, block, cover_block));
   int64_t* in_total = reinterpret_cast<int64_t*>(err + kCoverErrCount);
-  p->u_len = carve<uint32_t>(at, size_t(n));
-  p->u_sid = carve<uint32_t>(at, size_t(n));
-  p->u_koff = carve<uint32_t>(at, size_t(n));
-  p->lens = carve<uint32_t>(at, size_t(n));
-  p->sc_nodes = carve<uint32_t>(at, size_t(n));
-  p->sc_parent = carve<uint32_t>(at, size_t(n));
-  p->sc_rank = carve<uint32_t>(at, size_t(n));
-  p->edges = carve<uint32_t>(at, size_t(8 * n));
-  p->mate = carve<uint32_t>(at, size_t(2 * n));
-  p->best_w = carve<uint32_t>(at, size_t(2 * n));
-  p->best_prio = carve<unsigned long long>(at, size_t(2 * n));
-  p->visited = carve<uint8_t>(at, size_t(n));
-  p->scls = carve<uint8_t>(at, size_t(n));
-  p->u_flip = carve<uint8_t>(at, size_t(n));
-  p->s_nk = carve<int64_t>(at, size_t(n + 1));
-  p->sc01 = carve<int64_t>(at, size_t(n + 1));
-  p->sc2 = carve<int64_t>(at, size_t(n + 1));
-  p->str_start = carve<int64_t>(at, size_t(n + 1));
-  p->in_start = carve<int64_t>(at, size_t(n + 1));
-  uint64_t* first = carve<uint64_t>(at, size_t(n));
-  uint64_t* last = carve<uint64_t>(at, size_t(n));
-  unsigned long long* keys = carve<unsigned long long>(at, n_tables * cap);
-  uint32_t* vals = carve<uint32_t>(at, n_tables * cap);
-  KSH_BOUND(size_t(at - p->ublock) <= block);
   p->sc_used = &p->ctl->sc_used;
   EncCtl* ctl = p->ctl;
   hipStream_t st = ctx->stream;

@@ -26,7 +26,6 @@ constexpr int kFaThreads = 256;
 constexpr int kFaChunk = 64;
 constexpr int kFaSpan = kFaThreads * kFaChunk;
 
-inline size_t fa256(size_t x) { return (x + 255) & ~size_t(255); }
 inline unsigned fa_blocks(int64_t n, int per) { return unsigned(std::max<int64_t>(1, (n + per - 1) / per)); }
 
 __device__ __forceinline__ bool is_acgt(unsigned char ch) { return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; }
@@ -248,19 +247,24 @@ int ksh_fasta_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t 
   }
   hipStream_t st = ctx->stream;
   const int64_t n_chunks = (n_bytes + kFaChunk - 1) / kFaChunk;
-  const size_t per_chunk = fa256(size_t(n_chunks + 1) * 8);
-  KSH_TRY(arena_reserve(ctx, size_t(n_chunks / 256 + 4096) * 8 + (1u << 16) + 512));
-  arena_reset(ctx);
-  int* flags = static_cast<int*>(arena_alloc(ctx, 256));
-  if (!flags) return fail(KSH_INTERNAL, "scratch arena too small");
+  int* flags = nullptr;
+  // (the pad: the hand-written sum allowed 512 bytes for the flags)
+  KSH_TRY(arena_layout(ctx, scan_scratch_bytes(n_chunks), [&](Carver& c) { flags = c.take<int>(1); c.pad(256); }));
   KSH_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
-  // pass 1: per-chunk arrays (the fragment arrays follow once their count is known)
-  KSH_TRY(slot_reserve(ctx, kSlotText, 3 * per_chunk));
+  // The slot: three arrays per chunk and, behind them, three per fragment once their count is known (p->n_frag).
+  size_t per_chunk = 0, per_frag = 0;  // bytes of one array of either kind, as the list takes them
+  const auto fasta_slot = [&](Carver& c) {
+    p->nl_before = c.take<int64_t>(size_t(n_chunks + 1), &per_chunk);
+    p->starts_before = c.take<int64_t>(size_t(n_chunks + 1));
+    p->kept_before = c.take<int64_t>(size_t(n_chunks + 1));
+    if (p->n_frag == 0) return;
+    p->frag_start = c.take<int64_t>(size_t(p->n_frag + 1), &per_frag);
+    p->frag_end = c.take<int64_t>(size_t(p->n_frag + 1));
+    p->kept_idx = c.take<int64_t>(size_t(p->n_frag + 1));
+  };
+  // pass 1: per-chunk arrays
+  KSH_TRY(slot_layout(ctx, kSlotText, fasta_slot));
   ctx->text_slot_owner = 2;
-  char* at = ctx->slot[kSlotText];
-  p->nl_before = reinterpret_cast<int64_t*>(at);
-  p->starts_before = reinterpret_cast<int64_t*>(at + per_chunk);
-  p->kept_before = reinterpret_cast<int64_t*>(at + 2 * per_chunk);
   hipLaunchKernelGGL(k_fa_newlines, dim3(fa_blocks(n_chunks, 256)), dim3(256), 0, st, p->text, n_bytes,
                      p->nl_before);
   KSH_TRY(scan_exclusive_i64(ctx, p->nl_before, p->nl_before, n_chunks, p->nl_before + n_chunks));
@@ -286,14 +290,10 @@ int ksh_fasta_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t 
   // pass 2: fragments.  Their arrays go behind the per-chunk ones in the same slot; if that
   // makes the slot grow, its contents are lost and the two prefix arrays are recomputed (two
   // streaming passes).
-  const size_t per_frag = fa256(size_t(p->n_frag + 1) * 8);
+  (void)layout_bytes(fasta_slot);  // (per_frag, now that the count is known)
   const bool grows = 3 * per_chunk + 3 * per_frag > ctx->slot_bytes[kSlotText];
-  KSH_TRY(slot_reserve(ctx, kSlotText, 3 * per_chunk + 3 * per_frag));
-  at = ctx->slot[kSlotText];
+  KSH_TRY(slot_layout(ctx, kSlotText, fasta_slot));
   if (grows) {  // a fresh buffer: the two prefix arrays are gone
-    p->nl_before = reinterpret_cast<int64_t*>(at);
-    p->starts_before = reinterpret_cast<int64_t*>(at + per_chunk);
-    p->kept_before = reinterpret_cast<int64_t*>(at + 2 * per_chunk);
     hipLaunchKernelGGL(k_fa_newlines, dim3(fa_blocks(n_chunks, 256)), dim3(256), 0, st, p->text, n_bytes,
                        p->nl_before);
     KSH_TRY(scan_exclusive_i64(ctx, p->nl_before, p->nl_before, n_chunks, p->nl_before + n_chunks));
@@ -302,13 +302,9 @@ int ksh_fasta_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t 
     KSH_TRY(scan_exclusive_i64(ctx, p->starts_before, p->starts_before, n_chunks,
                                p->starts_before + n_chunks));
   }
-  p->frag_start = reinterpret_cast<int64_t*>(at + 3 * per_chunk);
-  p->frag_end = reinterpret_cast<int64_t*>(at + 3 * per_chunk + per_frag);
-  p->kept_idx = reinterpret_cast<int64_t*>(at + 3 * per_chunk + 2 * per_frag);
-  KSH_TRY(arena_reserve(ctx, per_frag + size_t(std::max(n_chunks, p->n_frag) / 256 + 4096) * 8 + (1u << 16)));
-  arena_reset(ctx);
-  int64_t* kept_len = static_cast<int64_t*>(arena_alloc(ctx, size_t(p->n_frag + 1) * 8));
-  if (!kept_len) return fail(KSH_INTERNAL, "scratch arena too small");
+  int64_t* kept_len = nullptr;
+  KSH_TRY(arena_layout(ctx, scan_scratch_bytes(std::max(n_chunks, p->n_frag)),
+                       [&](Carver& c) { kept_len = c.take<int64_t>(size_t(p->n_frag + 1)); }));
   hipLaunchKernelGGL(k_fa_ranges, dim3(fa_blocks(n_chunks, 256)), dim3(256), 0, st, p->text, n_bytes,
                      p->nl_before, p->starts_before, p->frag_start, p->frag_end);
   hipLaunchKernelGGL(k_fa_keep, dim3(fa_blocks(p->n_frag, 256)), dim3(256), 0, st, p->frag_start, p->frag_end,

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "kmersets_hip.h"
+#include "ksh_layout.h"
 
 namespace ksh {
 
@@ -155,9 +156,31 @@ int arena_reserve(ksh_ctx* ctx, size_t bytes);
 inline void arena_reset(ksh_ctx* ctx) { ctx->arena_used = 0; }
 // Returns nullptr when the arena is too small (callers reserve first).
 void* arena_alloc(ksh_ctx* ctx, size_t bytes);
+// The arena's next block, laid out by `layout` (ksh_layout.h): the block is as large as the list measures.
+template <typename Layout>
+int arena_carve(ksh_ctx* ctx, Layout&& layout) {
+  const size_t bytes = layout_bytes(layout);
+  if (!layout_bind(arena_alloc(ctx, bytes), bytes, layout)) return fail(KSH_INTERNAL, "scratch arena too small");
+  return KSH_OK;
+}
+// The usual start of a stage: the arena reserved for a layout and `extra` bytes behind it (what the stage's scans
+// take: scan_scratch_bytes), emptied, and the layout bound at its start.
+template <typename Layout>
+int arena_layout(ksh_ctx* ctx, size_t extra, Layout&& layout) {
+  KSH_TRY(arena_reserve(ctx, layout_bytes(layout) + extra));
+  arena_reset(ctx);
+  return arena_carve(ctx, layout);
+}
 int plan_reserve(ksh_ctx* ctx, size_t bytes);
 enum { kSlotDecode = 0, kSlotEncode = 1, kSlotText = 2 };
 int slot_reserve(ksh_ctx* ctx, int which, size_t bytes);
+// A slot reserved for what a layout measures, and the layout bound to it.
+template <typename Layout>
+int slot_layout(ksh_ctx* ctx, int which, Layout&& layout) {
+  KSH_TRY(slot_reserve(ctx, which, layout_bytes(layout)));
+  if (!layout_bind(ctx->slot[which], ctx->slot_bytes[which], layout)) return fail(KSH_INTERNAL, "scratch arena too small");
+  return KSH_OK;
+}
 // (thread-safe; a lane's jobs allocate what outlives them from lane->lane_parent's pool)
 int pool_alloc(ksh_ctx* ctx, size_t bytes, void** out);
 void pool_free(ksh_ctx* ctx, void* p);
@@ -174,7 +197,8 @@ int run_on_lanes(ksh_ctx* ctx, const std::vector<size_t>& order, size_t need_byt
                  const std::function<int(ksh_ctx*)>& prepare, const std::function<int(ksh_ctx*, size_t)>& job);
 inline ksh_ctx* result_ctx(ksh_ctx* lane) { return lane->lane_parent ? lane->lane_parent : lane; }
 
-// Scratch of an SPSS encode / decode of n k-mers (slot + arena bytes): what a lane reserves (ksh_encode.hip, ksh_decode.hip)
+// Scratch of an SPSS encode of n k-mers (slot + arena bytes, with the reserves' spare): what a lane reserves once, at
+// its largest n (ksh_encode.hip; non-decreasing in n, so that no smaller plan on the lane maps its slot again)
 size_t encode_scratch_bytes(const ksh_geom* g, int64_t n);
 int encode_reserve(ksh_ctx* ctx, const ksh_geom* g, int64_t n);
 
@@ -313,6 +337,8 @@ struct Timer {
 // (device, one int64, may be nullptr) receives the sum.  in may equal out.
 int scan_exclusive_i64(ksh_ctx* ctx, const int64_t* d_in, int64_t* d_out, int64_t n,
                        int64_t* d_total);
+// What one such scan of n values takes from the arena (its block sums, level by level, and their alignment).
+inline size_t scan_scratch_bytes(int64_t n) { return (size_t(n) / 256 + 4096) * sizeof(int64_t) + (1u << 16); }
 
 }  // namespace ksh
 

@@ -701,29 +701,31 @@ struct Plan {
   uint16_t* split = nullptr;     // max_tiles * kSplitPerTile: every chain's merge-path split (count pass -> write pass)
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-inline size_t plan_bytes(int64_t n_segs, int64_t max_tiles) {
-  return align256(size_t(n_segs + 1) * 8) + align256(size_t(max_tiles) * sizeof(TileDesc)) +
-         align256(size_t(max_tiles) * 8) + 256 + align256(size_t(max_tiles) * kSplitPerTile * 2) +
-         align256(size_t(max_tiles) * sizeof(TileOwner));
-}
-
-inline void plan_carve(char* base, int64_t n_segs, int64_t max_tiles, Plan* p) {
+inline void plan_layout(Carver& c, int64_t n_segs, int64_t max_tiles, Plan* p) {
   p->n_segs = n_segs;
   p->max_tiles = max_tiles;
-  char* at = base;
-  p->tile_base = reinterpret_cast<int64_t*>(at);
-  at += align256(size_t(n_segs + 1) * 8);
-  p->desc = reinterpret_cast<TileDesc*>(at);
-  at += align256(size_t(max_tiles) * sizeof(TileDesc));
-  p->tile_ioff = reinterpret_cast<int64_t*>(at);
-  at += align256(size_t(max_tiles) * 8);
-  p->total_m = reinterpret_cast<int64_t*>(at);
-  at += 256;
-  p->split = reinterpret_cast<uint16_t*>(at);
-  at += align256(size_t(max_tiles) * kSplitPerTile * 2);
-  p->owner = reinterpret_cast<TileOwner*>(at);
+  p->tile_base = c.take<int64_t>(size_t(n_segs + 1));
+  p->desc = c.take<TileDesc>(size_t(max_tiles));
+  p->tile_ioff = c.take<int64_t>(size_t(max_tiles));
+  p->total_m = c.take<int64_t>(1);
+  p->split = c.take<uint16_t>(size_t(max_tiles) * kSplitPerTile);
+  p->owner = c.take<TileOwner>(size_t(max_tiles));
+}
+
+inline size_t plan_bytes(int64_t n_segs, int64_t max_tiles) {
+  Plan p;
+  return layout_bytes([&](Carver& c) { plan_layout(c, n_segs, max_tiles, &p); });
+}
+
+// The plan's arrays in the block at `base`, of `reserved` bytes (ctx->plan, or a block of the arena).
+inline int plan_carve(void* base, size_t reserved, int64_t n_segs, int64_t max_tiles, Plan* p) {
+  if (!layout_bind(base, reserved, [&](Carver& c) { plan_layout(c, n_segs, max_tiles, p); }))
+    return fail(KSH_INTERNAL, "scratch arena too small");
+  return KSH_OK;
+}
+inline int plan_in_arena(ksh_ctx* ctx, int64_t n_segs, int64_t max_tiles, Plan* p) {
+  const size_t bytes = plan_bytes(n_segs, max_tiles);
+  return plan_carve(arena_alloc(ctx, bytes), bytes, n_segs, max_tiles, p);
 }
 
 template <typename KeyT, int kMode>
@@ -833,10 +835,10 @@ int pair_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const ks
   if (max_tiles > int64_t(0x7FFFFFF0)) return fail(KSH_INVALID_ARGUMENT, "pair too large for one launch");
   ctx->plan_kind = kPlanNone;  // ctx->plan is overwritten (or moved) from here on, whether this plan succeeds or not
   KSH_TRY(plan_reserve(ctx, plan_bytes(nb, max_tiles)));
-  KSH_TRY(arena_reserve(ctx, size_t(max_tiles / 256 + 4096) * 8 + (1u << 16)));
+  KSH_TRY(arena_reserve(ctx, scan_scratch_bytes(max_tiles)));
   arena_reset(ctx);
   Plan p;
-  plan_carve(ctx->plan, nb, max_tiles, &p);
+  KSH_TRY(plan_carve(ctx->plan, ctx->plan_bytes, nb, max_tiles, &p));
   BucketSegs<KeyT> segs{static_cast<const KeyT*>(a->d_keys), a->d_offsets,
                         static_cast<const KeyT*>(b->d_keys), b->d_offsets};
   KSH_TRY((plan_tile_base<KeyT>(ctx, segs, nb, p.tile_base, p.owner)));
@@ -863,7 +865,7 @@ int pair_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const k
   const int64_t nb = n_buckets(g);
   KSH_TRY(plan_claim(ctx, kPlanPair, g, a, b));
   Plan p;
-  plan_carve(ctx->plan, nb, ctx->plan_tiles, &p);
+  KSH_TRY(plan_carve(ctx->plan, ctx->plan_bytes, nb, ctx->plan_tiles, &p));
   {
     Timer timer(ctx, 0);
     launch_tile_merge<KeyT, 1>(ctx, p, nullptr, p.tile_ioff, p.split, static_cast<KeyT*>(d_keys_i),
@@ -876,7 +878,7 @@ int pair_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const k
 // Plan + write back to back with caller-provided upper-bound buffers: one stream sync
 // (for the totals) instead of two and no allocation between the passes.
 inline size_t pair_scratch_bytes(int64_t nb, int64_t max_tiles) {
-  return plan_bytes(nb, max_tiles) + size_t(max_tiles / 256 + 4096) * 8 + (1u << 16);
+  return plan_bytes(nb, max_tiles) + scan_scratch_bytes(max_tiles);
 }
 
 // Enqueues both passes of one pair; the three totals land in d_totals (device).  The scratch
@@ -888,9 +890,8 @@ int pair_algebra_enqueue(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a,
   const int64_t nb = n_buckets(g);
   const int64_t max_tiles = nb + (a->n_keys + b->n_keys) / TileCfg<KeyT>::kTile + 1;
   arena_reset(ctx);
-  char* base = static_cast<char*>(arena_alloc(ctx, plan_bytes(nb, max_tiles)));
   Plan p;
-  plan_carve(base, nb, max_tiles, &p);
+  KSH_TRY(plan_in_arena(ctx, nb, max_tiles, &p));
   BucketSegs<KeyT> segs{static_cast<const KeyT*>(a->d_keys), a->d_offsets,
                         static_cast<const KeyT*>(b->d_keys), b->d_offsets};
   KSH_TRY((plan_tile_base<KeyT>(ctx, segs, nb, p.tile_base, p.owner)));
@@ -922,14 +923,15 @@ int pair_algebra_batch_t(ksh_ctx* ctx, const ksh_geom* g, ksh_pair_job* jobs, in
   const int64_t n_segs = int64_t(n_jobs) * nb;
   if (max_tiles > int64_t(0x7FFFFFF0) || n_segs > int64_t(0x7FFFFFF0))
     return fail(KSH_INVALID_ARGUMENT, "batch too large for one launch");
-  const size_t pairs_bytes = align256(size_t(n_jobs) * sizeof(BatchPair));
-  KSH_TRY(arena_reserve(ctx, pairs_bytes + align256(size_t(n_jobs) * 24) + plan_bytes(n_segs, max_tiles) +
-                                 size_t(std::max(max_tiles, n_segs) / 256 + 4096) * 8 + (1u << 16)));
-  arena_reset(ctx);
-  BatchPair* d_pairs = static_cast<BatchPair*>(arena_alloc(ctx, size_t(n_jobs) * sizeof(BatchPair)));
-  int64_t* d_totals = static_cast<int64_t*>(arena_alloc(ctx, size_t(n_jobs) * 24));
-  char* base = static_cast<char*>(arena_alloc(ctx, plan_bytes(n_segs, max_tiles)));
-  if (!d_pairs || !d_totals || !base) return fail(KSH_INTERNAL, "scratch arena too small");
+  BatchPair* d_pairs = nullptr;
+  int64_t* d_totals = nullptr;
+  Plan p;
+  const auto batch_arena = [&](Carver& c) {
+    d_pairs = c.take<BatchPair>(size_t(n_jobs));
+    d_totals = c.take<int64_t>(size_t(n_jobs) * 3);
+    plan_layout(c, n_segs, max_tiles, &p);
+  };
+  KSH_TRY(arena_layout(ctx, scan_scratch_bytes(std::max(max_tiles, n_segs)), batch_arena));
   // the pair records and, later, the totals travel through one pinned buffer (a pageable source
   // would be staged by the runtime first); the stream is synchronised before this call returns,
   // so the buffer is free again by then
@@ -953,8 +955,6 @@ int pair_algebra_batch_t(ksh_ctx* ctx, const ksh_geom* g, ksh_pair_job* jobs, in
   }
   KSH_HIP(hipMemcpyAsync(d_pairs, h_pairs, size_t(n_jobs) * sizeof(BatchPair), hipMemcpyHostToDevice,
                          ctx->stream));
-  Plan p;
-  plan_carve(base, n_segs, max_tiles, &p);
   const BatchSegs<KeyT> segs{d_pairs, g->n_bucket_bits};
   KSH_TRY((plan_tile_base<KeyT>(ctx, segs, n_segs, p.tile_base, p.owner)));
   KSH_TRY((plan_count<KeyT>(ctx, segs, p, 1, true)));
@@ -1000,10 +1000,10 @@ int union_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const k
   if (max_tiles > int64_t(0x7FFFFFF0)) return fail(KSH_INVALID_ARGUMENT, "pair too large for one launch");
   ctx->plan_kind = kPlanNone;  // ctx->plan is overwritten (or moved) from here on, whether this plan succeeds or not
   KSH_TRY(plan_reserve(ctx, plan_bytes(nb, max_tiles)));
-  KSH_TRY(arena_reserve(ctx, size_t(max_tiles / 256 + 4096) * 8 + (1u << 16)));
+  KSH_TRY(arena_reserve(ctx, scan_scratch_bytes(max_tiles)));
   arena_reset(ctx);
   Plan p;
-  plan_carve(ctx->plan, nb, max_tiles, &p);
+  KSH_TRY(plan_carve(ctx->plan, ctx->plan_bytes, nb, max_tiles, &p));
   BucketSegs<KeyT> segs{static_cast<const KeyT*>(a->d_keys), a->d_offsets,
                         static_cast<const KeyT*>(b->d_keys), b->d_offsets};
   KSH_TRY((plan_tile_base<KeyT>(ctx, segs, nb, p.tile_base, p.owner)));
@@ -1027,7 +1027,7 @@ int union_write_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const 
   const int64_t nb = n_buckets(g);
   KSH_TRY(plan_claim(ctx, kPlanUnion, g, a, b));
   Plan p;
-  plan_carve(ctx->plan, nb, ctx->plan_tiles, &p);
+  KSH_TRY(plan_carve(ctx->plan, ctx->plan_bytes, nb, ctx->plan_tiles, &p));
   launch_tile_merge<KeyT, 2>(ctx, p, nullptr, p.tile_ioff, p.split, static_cast<KeyT*>(d_keys_u),
                              static_cast<KeyT*>(nullptr), static_cast<KeyT*>(nullptr));
   KSH_HIP(hipGetLastError());
@@ -1040,11 +1040,10 @@ int set_diff_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* a, const ksh
   const int64_t nb = n_buckets(g);
   const int64_t max_tiles = nb + (a->n_keys + b->n_keys) / TileCfg<KeyT>::kTile + 1;
   if (max_tiles > int64_t(0x7FFFFFF0)) return fail(KSH_INVALID_ARGUMENT, "pair too large for one launch");
-  KSH_TRY(arena_reserve(ctx, plan_bytes(nb, max_tiles) + size_t(max_tiles / 256 + 4096) * 8 + (1u << 16)));
+  KSH_TRY(arena_reserve(ctx, pair_scratch_bytes(nb, max_tiles)));
   arena_reset(ctx);
-  char* base = static_cast<char*>(arena_alloc(ctx, plan_bytes(nb, max_tiles)));
   Plan p;
-  plan_carve(base, nb, max_tiles, &p);
+  KSH_TRY(plan_in_arena(ctx, nb, max_tiles, &p));
   BucketSegs<KeyT> segs{static_cast<const KeyT*>(a->d_keys), a->d_offsets,
                         static_cast<const KeyT*>(b->d_keys), b->d_offsets};
   KSH_TRY((plan_tile_base<KeyT>(ctx, segs, nb, p.tile_base, p.owner)));
@@ -1073,19 +1072,18 @@ int pair_weights_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sets, in
     return KSH_OK;
   }
   // stage the descriptors
-  const size_t desc_bytes = align256(size_t(n_sets) * sizeof(SetPtrs)) +
-                            align256(size_t(n_ids) * 4) + align256(size_t(n_pairs) * 8) +
-                            align256(size_t(n_pairs) * 8);
-  const size_t base_bytes = align256(size_t(n_segs + 1) * 8);
-  KSH_TRY(arena_reserve(ctx, desc_bytes + base_bytes + size_t(n_segs / 256 + 4096) * 8 + (1u << 16)));
-  arena_reset(ctx);
-  SetPtrs* d_sets = static_cast<SetPtrs*>(arena_alloc(ctx, size_t(n_sets) * sizeof(SetPtrs)));
-  int32_t* d_ids = static_cast<int32_t*>(arena_alloc(ctx, size_t(n_ids) * 4));
-  int32_t* d_pairs = static_cast<int32_t*>(arena_alloc(ctx, size_t(n_pairs) * 8));
-  int64_t* d_weights = static_cast<int64_t*>(arena_alloc(ctx, size_t(n_pairs) * 8));
-  int64_t* tile_base = static_cast<int64_t*>(arena_alloc(ctx, size_t(n_segs + 1) * 8));
-  if (!d_sets || !d_ids || !d_pairs || !d_weights || !tile_base)
-    return fail(KSH_INTERNAL, "scratch arena too small");
+  SetPtrs* d_sets = nullptr;
+  int32_t *d_ids = nullptr, *d_pairs = nullptr;
+  int64_t *d_weights = nullptr, *tile_base = nullptr;
+  const auto staged_arena = [&](Carver& c) {
+    d_sets = c.take<SetPtrs>(size_t(n_sets));
+    d_ids = c.take<int32_t>(size_t(n_ids));
+    d_pairs = c.take<int32_t>(size_t(n_pairs) * 2);
+    d_weights = c.take<int64_t>(size_t(n_pairs));
+    tile_base = c.take<int64_t>(size_t(n_segs + 1));
+  };
+  KSH_TRY(arena_layout(ctx, scan_scratch_bytes(n_segs), staged_arena));
+  const size_t staged = ctx->arena_used;
   std::vector<SetPtrs> h_sets(static_cast<size_t>(n_sets));
   for (int32_t i = 0; i < n_sets; i++) h_sets[i] = SetPtrs{sets[i].d_keys, sets[i].d_offsets};
   KSH_HIP(hipMemcpyAsync(d_sets, h_sets.data(), size_t(n_sets) * sizeof(SetPtrs),
@@ -1102,15 +1100,15 @@ int pair_weights_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sets, in
   if (n_tiles > int64_t(0x7FFFFFF0)) return fail(KSH_INVALID_ARGUMENT, "too many tiles for one launch");
   // the remaining plan arrays: keep what is already in the arena, so grow by allocating a second
   // block if needed
-  const size_t rest = plan_bytes(0, n_tiles) + size_t(n_tiles / 256 + 4096) * 8 + (1u << 16);
+  const size_t rest = pair_scratch_bytes(0, n_tiles);
   if (ctx->arena_used + rest > ctx->arena_bytes) {
     // re-run with a bigger arena (descriptors are re-staged); rare: first call at a new size
-    KSH_TRY(arena_reserve(ctx, ctx->arena_used + rest + desc_bytes + base_bytes));
+    // (the hand-written request counted the staged arrays twice, the second time short of the last one's rounding)
+    KSH_TRY(arena_reserve(ctx, staged + rest + (staged - 256)));
     return pair_weights_t<KeyT>(ctx, g, sets, n_sets, bucket_ids, n_ids, pairs, n_pairs, weights);
   }
-  char* base = static_cast<char*>(arena_alloc(ctx, plan_bytes(0, n_tiles)));
   Plan p;
-  plan_carve(base, 0, n_tiles, &p);
+  KSH_TRY(plan_in_arena(ctx, 0, n_tiles, &p));
   p.n_segs = n_segs;
   p.tile_base = tile_base;
   KSH_TRY(label_tiles(ctx, tile_base, n_segs, p.owner));

@@ -243,17 +243,21 @@ int launch_join(ksh_kss_index* x, const uint64_t* d_kmers, int64_t n, int canon,
   const int anc_lds = anc_bytes <= size_t(kAncLdsBytes) ? 1 : 0;
   const size_t lds = size_t(kSliceBytes) + size_t(tile) * (8 + 8 * WT) + (anc_lds ? anc_bytes : 0);
 
-  const size_t need = 4 * 256 + size_t(nb) * 8 * 2 + size_t(nb + 1) * 8 * 2 + size_t(chunk) * 12 + size_t(nb) / 32 +
-                      (1u << 16);
-  KSH_TRY(arena_reserve(ctx, need));
-  arena_reset(ctx);
-  auto* cnt = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb) * 8));
-  auto* cursor = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb) * 8));
-  auto* start = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb + 1) * 8));
-  auto* tstart = static_cast<int64_t*>(arena_alloc(ctx, size_t(nb + 1) * 8));
-  auto* pkey = static_cast<uint64_t*>(arena_alloc(ctx, size_t(chunk) * 8));
-  auto* pidx = static_cast<uint32_t*>(arena_alloc(ctx, size_t(chunk) * 4));
-  if (!cnt || !cursor || !start || !tstart || !pkey || !pidx) return fail(KSH_INTERNAL, "scratch arena too small");
+  int64_t *cnt = nullptr, *cursor = nullptr, *start = nullptr, *tstart = nullptr;
+  uint64_t* pkey = nullptr;
+  uint32_t* pidx = nullptr;
+  const auto join_arena = [&](Carver& c) {
+    cnt = c.take<int64_t>(size_t(nb));
+    cursor = c.take<int64_t>(size_t(nb));
+    start = c.take<int64_t>(size_t(nb + 1));
+    tstart = c.take<int64_t>(size_t(nb + 1));
+    pkey = c.take<uint64_t>(size_t(chunk));
+    pidx = c.take<uint32_t>(size_t(chunk));
+  };
+  // Behind the arrays: the sums of the scans over nb.  The request stays the hand-written one -- the unrounded arrays,
+  // 4 * 256 for their alignment, nb / 32 + 64 KiB for the sums: the list's roundings (under 1536 bytes) come out of those.
+  const size_t was = 4 * 256 + size_t(nb) * 8 * 2 + size_t(nb + 1) * 8 * 2 + size_t(chunk) * 12 + size_t(nb) / 32 + (1u << 16);
+  KSH_TRY(arena_layout(ctx, was - layout_bytes(join_arena), join_arena));
   const size_t scan_mark = ctx->arena_used;  // the scans below carve their own sums after this point
 
   for (int64_t base = 0; base < n; base += chunk) {

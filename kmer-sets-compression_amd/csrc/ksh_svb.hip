@@ -85,11 +85,12 @@ __global__ __launch_bounds__(256) void k_svb_decode(const uint8_t* __restrict__ 
 }
 
 static int svb_plan(ksh_ctx* ctx, int64_t n_groups, int64_t** sizes, int64_t** total) {
-  KSH_TRY(arena_reserve(ctx, size_t(n_groups + 8) * 8 + size_t(n_groups / 256 + 4096) * 8 + (1u << 16)));
+  // one array (sizes, the total behind them) in front of the scan's sums; 56 bytes spare
+  KSH_TRY(arena_reserve(ctx, size_t(n_groups + 8) * 8 + scan_scratch_bytes(n_groups)));
   arena_reset(ctx);
   *sizes = static_cast<int64_t*>(arena_alloc(ctx, size_t(n_groups + 1) * 8));
-  *total = *sizes + n_groups;
   if (!*sizes) return fail(KSH_INTERNAL, "scratch arena too small");
+  *total = *sizes + n_groups;
   return KSH_OK;
 }
 

@@ -26,7 +26,6 @@ constexpr int kChunk = 64;                               // bases (to text) / by
 constexpr int kSpan = kTextThreads * kChunk;             // per workgroup
 constexpr int kTextLds = kSpan + kSpan / 4 + 64;         // + one newline per >= 4 bases (K >= 4) + slack
 
-inline size_t a256(size_t x) { return (x + 255) & ~size_t(255); }
 inline unsigned blocks_of(int64_t n, int per) { return unsigned(std::max<int64_t>(1, (n + per - 1) / per)); }
 
 __global__ __launch_bounds__(256) void k_text_str_bases(const uint32_t* __restrict__ lens, int64_t n, int k,
@@ -209,15 +208,14 @@ int ksh_spss_to_text(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, ch
   if (s->n_strings == 0 || s->n_bases == 0) return KSH_OK;
   if (!s->d_words || !s->d_lens || !d_text) return fail(KSH_INVALID_ARGUMENT, "NULL buffer");
   const int64_t n_chunks = (s->n_bases + kChunk - 1) / kChunk;
-  const size_t bytes = a256(size_t(s->n_strings + 1) * 8) + a256(size_t(n_chunks) * 8) +
-                       a256(size_t(n_chunks + 1) * 8) + size_t(std::max(s->n_strings, n_chunks) / 256 + 4096) * 8 +
-                       (1u << 16);
-  KSH_TRY(arena_reserve(ctx, bytes));
-  arena_reset(ctx);
-  int64_t* str_start = static_cast<int64_t*>(arena_alloc(ctx, size_t(s->n_strings + 1) * 8));
-  unsigned long long* end_bits = static_cast<unsigned long long*>(arena_alloc(ctx, size_t(n_chunks) * 8));
-  int64_t* ends_before = static_cast<int64_t*>(arena_alloc(ctx, size_t(n_chunks + 1) * 8));
-  if (!str_start || !end_bits || !ends_before) return fail(KSH_INTERNAL, "scratch arena too small");
+  int64_t *str_start = nullptr, *ends_before = nullptr;
+  unsigned long long* end_bits = nullptr;
+  const auto text_arena = [&](Carver& c) {
+    str_start = c.take<int64_t>(size_t(s->n_strings + 1));
+    end_bits = c.take<unsigned long long>(size_t(n_chunks));
+    ends_before = c.take<int64_t>(size_t(n_chunks + 1));
+  };
+  KSH_TRY(arena_layout(ctx, scan_scratch_bytes(std::max(s->n_strings, n_chunks)), text_arena));
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(k_text_str_bases, dim3(blocks_of(s->n_strings, 256)), dim3(256), 0, st, s->d_lens,
                      s->n_strings, g->k, str_start);
@@ -268,14 +266,13 @@ int ksh_spss_from_text_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text,
     return KSH_OK;
   }
   const int64_t n_chunks = (n_bytes + kChunk - 1) / kChunk;
-  KSH_TRY(arena_reserve(ctx, size_t(n_chunks / 256 + 4096) * 8 + (1u << 16) + 512));
-  arena_reset(ctx);
-  int* flags = static_cast<int*>(arena_alloc(ctx, 256));
+  int* flags = nullptr;
+  // (the pad: the hand-written sum allowed 512 bytes for the flags)
+  KSH_TRY(arena_layout(ctx, scan_scratch_bytes(n_chunks), [&](Carver& c) { flags = c.take<int>(1); c.pad(256); }));
   hipStream_t st = ctx->stream;
   // nl_before lives in the text slot: it is needed again by ksh_spss_from_text_write
-  KSH_TRY(slot_reserve(ctx, kSlotText, a256(size_t(n_chunks + 1) * 8)));
+  KSH_TRY(slot_layout(ctx, kSlotText, [&](Carver& c) { p->nl_before = c.take<int64_t>(size_t(n_chunks + 1)); }));
   ctx->text_slot_owner = 1;
-  p->nl_before = reinterpret_cast<int64_t*>(ctx->slot[kSlotText]);
   KSH_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_text_count_nl, dim3(blocks_of(n_chunks, 256)), dim3(256), 0, st, p->text, n_bytes,
                      p->nl_before, flags);
@@ -311,11 +308,13 @@ static int from_text_write_entry(ksh_ctx* ctx, uint64_t* d_words, uint32_t* d_le
   ctx->text_written = true;
   if (p->n_lines == 0) return KSH_OK;
   const int64_t n_chunks = (p->n_bytes + kChunk - 1) / kChunk;
-  KSH_TRY(arena_reserve(ctx, a256(size_t(p->n_lines) * 8) + 512));
-  arena_reset(ctx);
-  int* flags = static_cast<int*>(arena_alloc(ctx, 256));
-  int64_t* line_end = static_cast<int64_t*>(arena_alloc(ctx, size_t(p->n_lines) * 8));
-  if (!flags || !line_end) return fail(KSH_INTERNAL, "scratch arena too small");
+  int* flags = nullptr;
+  int64_t* line_end = nullptr;
+  KSH_TRY(arena_layout(ctx, 0, [&](Carver& c) {
+    flags = c.take<int>(1);
+    line_end = c.take<int64_t>(size_t(p->n_lines));
+    c.pad(256);  // the hand-written sum allowed 512 bytes for the flags
+  }));
   hipStream_t st = ctx->stream;
   KSH_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_text_line_ends, dim3(blocks_of(n_chunks, 256)), dim3(256), 0, st, p->text, p->n_bytes,
