@@ -34,7 +34,10 @@ constexpr int64_t kFirstCopy = 4096;  // classes read back with the call's one s
 constexpr int kCtlWords = 4;
 
 // LDS of k_color_classes: the walk, the class table (4 words per slot), occupancy and stop flag.
-size_t classes_lds_bytes(int n_nodes) { return walk_lds_bytes(n_nodes) + size_t(kClsSlots) * 32 + 8; }
+constexpr size_t classes_lds_bytes(int n_nodes) { return walk_lds_bytes(n_nodes) + size_t(kClsSlots) * 32 + 8; }
+constexpr size_t kClassesLdsMax = classes_lds_bytes(kMaxNodes);  // what the kernel opts in to
+static_assert(kClassesLdsMax == 77904 && 2 * kClassesLdsMax <= (160u << 10),
+              "76 KiB at 1024 nodes (over 64 KiB from 406 nodes on): two workgroups per CU at any node count");
 
 }  // namespace
 
@@ -84,8 +87,8 @@ __device__ __forceinline__ unsigned long long cls_peek(const unsigned long long*
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Every entry of the workgroup's table into the global one; the table is left empty.  Callers put a barrier before
-// it (the table is complete) and after it.  Once the call has failed (ctl[1]) nothing more is inserted.
+// Every entry of the workgroup's table into the global one; the table is left empty.  Called behind a tile's
+// closing barrier (the table is complete); a barrier follows before the table is inserted into again.  Once the call has failed (ctl[1]) nothing more is inserted.
 __device__ __forceinline__ void cls_spill(unsigned long long* c_tab, unsigned long long* __restrict__ g_tab,
                                           uint32_t g_mask, int64_t capacity, unsigned long long* __restrict__ ctl) {
   for (int s = threadIdx.x; s < kClsSlots; s += kThreads) {
@@ -108,95 +111,74 @@ __device__ __forceinline__ void cls_spill(unsigned long long* c_tab, unsigned lo
   }
 }
 
-// flags[1]: some bucket was cut by key range; flags[3]: some workgroup spilled its class table before its last tile.
-template <typename KeyT>
-__global__ __launch_bounds__(kThreads) void k_color_classes(const NodeRef* __restrict__ nodes, int n_nodes,
-                                                            const uint64_t* __restrict__ proj, int64_t nb,
-                                                            int key_bits, unsigned long long* __restrict__ g_tab,
-                                                            uint32_t g_mask, int64_t capacity,
-                                                            unsigned long long* __restrict__ ctl,
-                                                            int* __restrict__ flags) {
-  extern __shared__ unsigned long long cls_lds[];
-  unsigned long long* t_key = cls_lds;
-  unsigned long long* t_row = t_key + kSlots;
-  unsigned long long* c_tab = t_row + 2 * kSlots;
-  long long* s_cur = reinterpret_cast<long long*>(c_tab + 4 * kClsSlots);
-  long long* s_end = s_cur + n_nodes;
-  unsigned long long* s_red = reinterpret_cast<unsigned long long*>(s_end + n_nodes);
-  int* s_ctl = reinterpret_cast<int*>(s_red + 8);  // [0] slots of c_tab that are taken, [1] the call has failed
-  int* s_pre = s_ctl + 2;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const TileWalk w{t_key, t_row, s_cur, s_end, s_red, s_pre};
-  pc_table_clear(w);
-  for (int t = tid; t < 4 * kClsSlots; t += kThreads) c_tab[t] = 0;
-  if (tid == 0) s_ctl[0] = s_ctl[1] = 0;
-  __syncthreads();
-
-  const uint64_t key_max = (uint64_t(1) << key_bits) - 1;
-  bool pending = false;  // the class table is spilled before the next tile is counted
+// The class consumer of the walk.  flags[3]: the workgroup spilled its class table before its last tile.
+struct ClassConsumer {
+  unsigned long long* g_tab;
+  uint32_t g_mask;
+  int64_t capacity;
+  unsigned long long* ctl;
+  unsigned long long* c_tab = nullptr;  // LDS: kClsSlots slots in four planes
+  int* s_ctl = nullptr;                 // LDS: [0] slots of c_tab that are taken, [1] the call has failed
+  bool pending = false;  // the class table is spilled before the next tile is counted (uniform: s_ctl[0] is read
+                         // behind a tile's closing barrier)
   bool lost = false;     // (cannot happen) a row found no slot in c_tab
 
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    // (written before the barriers of pc_bucket_begin and read after them; read only where a tile, and so a
-    // barrier, follows before thread 0 can write it again)
-    if (tid == 0) s_ctl[1] = cls_peek(&ctl[1]) != 0;
-    int64_t left = pc_bucket_begin(nodes, n_nodes, b, w);
-    if (left == 0) continue;  // (uniform)
-    if (s_ctl[1]) break;      // (uniform) more classes than capacity: the call fails whatever else is counted
-    bool cut = false;
-    while (left > 0) {
-      const int total = pc_tile_cut<KeyT>(nodes, n_nodes, w, left, key_max, &cut, flags);
-
-      if (pending) {  // (uniform: s_ctl[0] was read behind a barrier)
-        cls_spill(c_tab, g_tab, g_mask, capacity, ctl);
-        if (tid == 0) {
-          flags[3] = 1;
-          s_ctl[0] = 0;
-        }
-        pending = false;
-        __syncthreads();
-      }
-
-      pc_tile_fill<KeyT>(nodes, n_nodes, proj, w, total);
-
-      // a lane takes a slot and leaves it empty; one (row, count) per wave and distinct row goes to c_tab
-      for (int slot = tid; slot < kSlots; slot += kThreads) {
-        const bool occ = t_key[slot] != kEmpty;
-        uint64_t r0 = 0, r1 = 0;
-        if (occ) {
-          r0 = t_row[2 * slot];
-          r1 = t_row[2 * slot + 1];
-          t_key[slot] = kEmpty;
-          t_row[2 * slot] = 0;
-          t_row[2 * slot + 1] = 0;
-        }
-        unsigned long long todo = __ballot(occ);
-        int mine = 0;  // leaders: the lanes of this round that hold my row
-        while (todo) {
-          const int leader = __ffsll(todo) - 1;
-          const uint64_t l0 = __shfl(static_cast<unsigned long long>(r0), leader, 64);
-          const uint64_t l1 = __shfl(static_cast<unsigned long long>(r1), leader, 64);
-          const unsigned long long same = __ballot(occ && r0 == l0 && r1 == l1);
-          if (lane == leader) mine = __popcll(same);
-          todo &= ~same;
-        }
-        if (mine) {  // the leaders insert side by side: cls_insert never waits
-          int claims = 0;
-          if (!cls_insert<1, kClsSlots>(c_tab, kClsSlots - 1, r0, r1, static_cast<unsigned long long>(mine), &claims))
-            lost = true;
-          if (claims) atomicAdd(&s_ctl[0], claims);
-        }
-      }
-      __syncthreads();
-
-      left -= total;
-      pending = s_ctl[0] > kClsSpill;
+  __device__ __forceinline__ void bind(const TileWalk&, OwnLds* own) {
+    c_tab = pc_own<unsigned long long>(own, 4 * kClsSlots);
+    s_ctl = pc_own<int>(own, 2);
+  }
+  // (s_ctl[1] is written ahead of the barriers of the bucket's begin and read behind them; it is read only in a
+  // bucket that has entries, so a tile, and with it a barrier, follows before thread 0 writes it again)
+  __device__ __forceinline__ void bucket_next(int64_t) {
+    if (threadIdx.x == 0) s_ctl[1] = cls_peek(&ctl[1]) != 0;
+  }
+  __device__ __forceinline__ Bucket bucket_begun(int64_t, int64_t left) {
+    if (left == 0) return Bucket::kSkip;
+    // more classes than capacity: the call fails whatever else is counted
+    return s_ctl[1] ? Bucket::kStop : Bucket::kWalk;
+  }
+  __device__ __forceinline__ bool settle(int* flags) {
+    if (!pending) return false;
+    cls_spill(c_tab, g_tab, g_mask, capacity, ctl);
+    if (threadIdx.x == 0) {
+      flags[3] = 1;
+      s_ctl[0] = 0;
+    }
+    pending = false;
+    return true;
+  }
+  // one (row, count) per wave and distinct row of the round goes to c_tab
+  __device__ __forceinline__ void slot(const Slot& s) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(s.occ);
+    int mine = 0;  // leaders: the lanes of this round that hold my row
+    while (todo) {
+      const int leader = __ffsll(todo) - 1;
+      const uint64_t l0 = __shfl(static_cast<unsigned long long>(s.r0), leader, 64);
+      const uint64_t l1 = __shfl(static_cast<unsigned long long>(s.r1), leader, 64);
+      const unsigned long long same = __ballot(s.occ && s.r0 == l0 && s.r1 == l1);
+      if (lane == leader) mine = __popcll(same);
+      todo &= ~same;
+    }
+    if (mine) {  // the leaders insert side by side: cls_insert never waits
+      int claims = 0;
+      if (!cls_insert<1, kClsSlots>(c_tab, kClsSlots - 1, s.r0, s.r1, static_cast<unsigned long long>(mine), &claims))
+        lost = true;
+      if (claims) atomicAdd(&s_ctl[0], claims);
     }
   }
-  // (the table is complete: the last barrier was a tile's, or no tile was counted)
-  cls_spill(c_tab, g_tab, g_mask, capacity, ctl);
-  if (lost) atomicAdd(&ctl[3], 1ull);
+  __device__ __forceinline__ void tile_done(int) { pending = s_ctl[0] > kClsSpill; }
+  __device__ __forceinline__ void bucket_done(int64_t) {}
+  // (the table is complete: the last barrier was a tile's closing one, or no tile was counted)
+  __device__ __forceinline__ void finish() {
+    cls_spill(c_tab, g_tab, g_mask, capacity, ctl);
+    if (lost) atomicAdd(&ctl[3], 1ull);
+  }
+};
+
+template <typename KeyT>
+__global__ __launch_bounds__(kThreads) void k_color_classes(WalkArgs a, ClassConsumer c) {
+  pc_walk<KeyT>(a, c);
 }
 
 // The occupied slots of the global table, packed as (r0, r1, count) in any order: out[3 c ..], c < capacity;
@@ -228,24 +210,9 @@ __global__ __launch_bounds__(256) void k_class_pack(const unsigned long long* __
 template <typename KeyT>
 static int launch_classes(ksh_ctx* ctx, const IndexShape& x, const uint64_t* proj, unsigned long long* g_tab,
                           int64_t slots, int64_t capacity, unsigned long long* ctl) {
-  const size_t lds = classes_lds_bytes(x.n_nodes);
-  const uint32_t bit = 512u << (sizeof(KeyT) == 2 ? 0 : sizeof(KeyT) == 4 ? 1 : 2);
-  if (lds > (64u << 10) && !(ctx->lds_opt_in & bit)) {  // (more than the 64 KB a kernel gets without asking)
-    KSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_color_classes<KeyT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, int(classes_lds_bytes(1024))));
-    ctx->lds_opt_in |= bit;
-  }
-  int n_cu = 0;
-  KSH_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  const int64_t nb = n_buckets(&x.g);
-  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, int64_t(160 << 10) / int64_t(lds)));
-  const int64_t want = (x.total_keys + kRowsPerGroup - 1) / kRowsPerGroup;
-  const int64_t grid = std::max<int64_t>(1, std::min({want, nb, per_cu * n_cu}));
-  hipLaunchKernelGGL((k_color_classes<KeyT>), dim3(unsigned(grid)), dim3(kThreads), lds, ctx->stream,
-                     static_cast<const NodeRef*>(x.d_nodes), x.n_nodes, proj, nb, key_bits(&x.g), g_tab,
-                     uint32_t(slots - 1), capacity, ctl, x.d_flags);
-  KSH_HIP(hipGetLastError());
-  return KSH_OK;
+  return walk_launch(ctx, x, proj, k_color_classes<KeyT>, classes_lds_bytes(x.n_nodes), kClassesLdsMax,
+                     lds_opt_in_bit<KeyT>(kLdsClasses),
+                     ClassConsumer{g_tab, uint32_t(slots - 1), capacity, ctl});
 }
 
 }  // namespace ksh
@@ -261,42 +228,21 @@ extern "C" int ksh_kss_color_classes(const int32_t* cols, int32_t n_cols, ksh_ks
   if (capacity < 1 || capacity > kMaxCapacity)
     return fail(KSH_INVALID_ARGUMENT, "capacity = %lld is outside [1, %lld]", (long long)capacity,
                 (long long)kMaxCapacity);
-  if (cols && (n_cols < 1 || n_cols > kMaxCols))
-    return fail(KSH_INVALID_ARGUMENT, "n_cols = %d is outside [1, %d]", n_cols, kMaxCols);
+  KSH_TRY(check_col_count(cols, n_cols, "cols"));
   const IndexShape x = index_shape(idx);
   ColList list{};
-  if (!cols) {
-    if (x.n_nodes > kMaxCols)
-      return fail(KSH_INVALID_ARGUMENT, "cols is NULL (all nodes) but the index has %d nodes, more than %d columns: "
-                                        "name the columns of each call", x.n_nodes, kMaxCols);
-    n_cols = x.n_nodes;
-    for (int32_t c = 0; c < n_cols; c++) list.id[c] = c;
-  } else {
-    std::vector<char> seen(size_t(x.n_nodes), 0);
-    for (int32_t c = 0; c < n_cols; c++) {
-      const int32_t id = cols[c];
-      if (id < 0 || id >= x.n_nodes)
-        return fail(KSH_INVALID_ARGUMENT, "cols[%d] = %d is outside [0, %d)", c, id, x.n_nodes);
-      if (seen[size_t(id)]) return fail(KSH_INVALID_ARGUMENT, "cols[%d] = %d is repeated", c, id);
-      seen[size_t(id)] = 1;
-      list.id[c] = id;
-    }
-  }
+  KSH_TRY(resolve_cols(cols, n_cols, x, "cols", &list, &n_cols));
   ksh_ctx* ctx = x.ctx;
-  KSH_HIP(hipSetDevice(ctx->device));
+  PoolBuf proj(ctx), tab(ctx), res(ctx);
+  KSH_TRY(walk_prologue(idx, x, list, n_cols, &proj));
   int64_t slots = 2;
   while (slots < 2 * capacity) slots <<= 1;
-  PoolBuf proj(ctx), tab(ctx), res(ctx);
-  KSH_TRY(pool_alloc(ctx, size_t(std::max(x.n_nodes, 1)) * 16, &proj.p));
   KSH_TRY(pool_alloc(ctx, size_t(slots) * 32, &tab.p));
   KSH_TRY(pool_alloc(ctx, (size_t(kCtlWords) + 3 * size_t(capacity)) * 8, &res.p));
   auto* g_tab = static_cast<unsigned long long*>(tab.p);
   auto* ctl = static_cast<unsigned long long*>(res.p);
-  index_set_routes(idx, 0);
-  KSH_HIP(hipMemsetAsync(x.d_flags, 0, 16, ctx->stream));
   KSH_HIP(hipMemsetAsync(g_tab, 0, size_t(slots) * 32, ctx->stream));
   KSH_HIP(hipMemsetAsync(ctl, 0, size_t(kCtlWords) * 8, ctx->stream));
-  KSH_TRY(pair_project(ctx, x, list, n_cols, static_cast<uint64_t*>(proj.p)));
   KSH_TRY(KSH_BY_KEY(x.g.key_bytes, launch_classes, ctx, x, static_cast<const uint64_t*>(proj.p), g_tab, slots,
                      capacity, ctl));
   const int64_t pack_grid = std::max<int64_t>(1, std::min<int64_t>((slots + 255) / 256, 4096));

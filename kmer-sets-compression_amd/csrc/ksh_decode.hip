@@ -978,7 +978,7 @@ int scatter_sort(ksh_ctx* ctx, const ksh_spss_view* s, const DecodeState& st, in
   }));
   {
     // (more than the 64 KB a kernel gets without asking)
-    const uint32_t bit = 8u << (sizeof(KeyT) == 2 ? 0 : sizeof(KeyT) == 4 ? 1 : 2);
+    const uint32_t bit = lds_opt_in_bit<KeyT>(kLdsBucketSort);
     if (!(ctx->lds_opt_in & bit)) {
       KSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket_sort<KeyT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, kSortLdsBytes));

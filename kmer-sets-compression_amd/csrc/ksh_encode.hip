@@ -3914,7 +3914,7 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
       const size_t hist_lds = size_t(ng) * 4;
       {
         // (more than the 64 KB a kernel gets without asking; per context: the attribute is the device's)
-        const uint32_t bit = 1u << (sizeof(KeyT) == 2 ? 0 : sizeof(KeyT) == 4 ? 1 : 2);
+        const uint32_t bit = lds_opt_in_bit<KeyT>(kLdsRcProbe);
         if (!(ctx->lds_opt_in & bit)) {
           const int bytes = int(kRcWindowBytes + 2048);
           KSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_adj_rc<KeyT, 1024>),

@@ -45,6 +45,15 @@ int fail(int code, const char* fmt, ...);
 
 constexpr int kNumTimers = 8;
 
+// The bits of ksh_ctx::lds_opt_in.  A kernel family takes three from its first, one per key width (u16, u32, u64):
+// the encode's staged neighbour probe (ksh_encode.hip), k_bucket_sort (ksh_decode.hip), k_pair_gram
+// (ksh_paircounts.hip), k_color_classes (ksh_classes.hip).
+constexpr uint32_t kLdsRcProbe = 1u << 0, kLdsBucketSort = 1u << 3, kLdsPairGram = 1u << 6, kLdsClasses = 1u << 9;
+template <typename KeyT>
+constexpr uint32_t lds_opt_in_bit(uint32_t family) {
+  return family << (sizeof(KeyT) == 2 ? 0 : sizeof(KeyT) == 4 ? 1 : 2);
+}
+
 }  // namespace ksh
 
 // Scratch arena: one growing device buffer, carved by bump allocation and reset
@@ -82,7 +91,8 @@ struct ksh_ctx {
   void* enc_state = nullptr;
 
   // kernels of this context's device that have been granted more than 64 KB of dynamic LDS
-  // (hipFuncSetAttribute acts on the current device: once per context, not once per process)
+  // (hipFuncSetAttribute acts on the current device: once per context, not once per process): a bit per kernel
+  // family and key width, ksh::lds_opt_in_bit<KeyT>(family)
   uint32_t lds_opt_in = 0;
 
   // text -> SPSS plan state (ksh_text.hip), FASTA -> fragments plan state (ksh_fasta.hip);

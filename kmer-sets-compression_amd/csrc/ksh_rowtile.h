@@ -1,18 +1,18 @@
 // The tile walk over a KmerSetSet index that ksh_kss_pair_counts (ksh_paircounts.hip), ksh_kss_select_*
-// (ksh_select.hip) and ksh_kss_color_classes (ksh_classes.hip) share.  gfx950 only.
+// (ksh_select.hip) and ksh_kss_color_classes (ksh_classes.hip) share, and the host
+// side of the three calls (ksh_rowtile.hip).  gfx950 only.
 //
 // A workgroup of kThreads walks one bucket at a time.  A bucket whose entries (all nodes together) fit a tile is
 // one tile; otherwise the workgroup walks the bucket's key range left to right and cuts it by key: every tile is
 // "all remaining entries with key <= c", so the tiles of a bucket are ordered and no key straddles two of them.
 // A tile's distinct keys and their rows over the chosen columns (the OR of proj[j] over the nodes j that hold the
-// key) are formed in an LDS hash table: atomicCAS on the key, atomicOr on the row.  What is done with the occupied
-// slots is the caller's; it leaves every slot empty (kEmpty, zero row) for the next tile.
+// key) are formed in an LDS hash table: atomicCAS on the key, atomicOr on the row.
 //
-// Callers rely on the barriers inside the walk: pc_bucket_begin and pc_tile_cut each pass at least one
-// __syncthreads() in every thread, on every path (pc_block_sum, pc_prefix), and pc_tile_fill one between its two
-// loops.  k_color_classes has thread 0 write an LDS flag ahead of pc_bucket_begin that all threads read after it,
-// and reads its table's occupancy behind pc_tile_cut.  An edit that takes a barrier out of one of the three must
-// give those callers one of their own.
+// The walk is one function, pc_walk: the loop over buckets, the loop over tiles and every __syncthreads() of the
+// walk are in it, and a kernel is pc_walk with a consumer object whose hooks say what is done with the rows.  What
+// each hook may rely on -- which barrier lies before it and which behind it -- is stated at pc_walk, hook by hook;
+// a consumer that needs a barrier pc_walk does not promise there passes one of its own.  The walk's LDS is placed
+// by walk_layout, for the launch's byte count and the kernel's pointers alike; a consumer's own LDS lies behind it.
 #ifndef KSH_ROWTILE_H_
 #define KSH_ROWTILE_H_
 
@@ -45,8 +45,21 @@ struct PoolBuf {
   PoolBuf& operator=(const PoolBuf&) = delete;
 };
 
-// The LDS of a walk, carved by the kernel: the table (kSlots keys, 2 * kSlots row words), per node the cursor and
-// the end of its slice of the bucket, 8 words for the reductions, and n_nodes + 1 ints for the tile's prefix.
+// The LDS of a walk, first in every kernel's dynamic LDS: the table (kSlots keys, 2 * kSlots row words), per node
+// the cursor and the end of its slice of the bucket, 8 words for the reductions, and n_nodes + 1 ints for the
+// tile's prefix (rounded to whole 8-byte words).  Offsets in 8-byte words; `own` is where the consumer's region
+// starts.
+struct WalkLayout { size_t t_key, t_row, s_cur, s_end, s_red, s_pre, own; };
+__host__ __device__ constexpr WalkLayout walk_layout(int n_nodes) {
+  const size_t n = size_t(n_nodes), cur = 3 * size_t(kSlots), red = cur + 2 * n;
+  return WalkLayout{0, kSlots, cur, cur + n, red, red + 8, red + 8 + (n + 2) / 2};
+}
+// A consumer's launch passes walk_lds_bytes(n_nodes) + the bytes of what it takes with pc_own.
+constexpr size_t walk_lds_bytes(int n_nodes) { return walk_layout(n_nodes).own * 8; }
+constexpr int kMaxNodes = 1024;  // the node count the LDS budgets are quoted at
+static_assert(walk_lds_bytes(kMaxNodes) == 45128 && walk_lds_bytes(127) == 27184, "the walk's LDS: 24 KiB + 64 + "
+              "20 bytes per node, the prefix rounded to 8");
+
 struct TileWalk {
   unsigned long long* t_key;
   unsigned long long* t_row;
@@ -55,8 +68,23 @@ struct TileWalk {
   unsigned long long* s_red;
   int* s_pre;
 };
-constexpr size_t walk_lds_bytes(int n_nodes) {
-  return size_t(kSlots) * 24 + size_t(n_nodes) * 16 + 8 * 8 + size_t((n_nodes + 2) & ~1) * 4;
+// The consumer's region behind the walk's arrays, and the bytes of it that pc_own has handed out.
+struct OwnLds { unsigned long long* base; size_t bytes; };
+// The walk's arrays in the kernel's dynamic LDS; *own = the consumer's region, nothing of it taken.
+__device__ __forceinline__ TileWalk walk_bind(unsigned long long* lds, int n_nodes, OwnLds* own) {
+  const WalkLayout l = walk_layout(n_nodes);
+  *own = OwnLds{lds + l.own, 0};
+  return TileWalk{lds + l.t_key, lds + l.t_row, reinterpret_cast<long long*>(lds + l.s_cur),
+                  reinterpret_cast<long long*>(lds + l.s_end), lds + l.s_red, reinterpret_cast<int*>(lds + l.s_pre)};
+}
+// The next n elements of type T of the consumer's region, from the next 8-byte boundary on.  at->bytes ends exactly
+// behind them: what a consumer has taken is what its byte count adds to walk_lds_bytes, to the byte, provided the
+// count lists the same arrays in the same order (an array of 4-byte elements that is not the last rounds to 8).
+template <typename T>
+__device__ __forceinline__ T* pc_own(OwnLds* at, size_t n) {
+  const size_t from = (at->bytes + 7) & ~size_t(7);
+  at->bytes = from + n * sizeof(T);
+  return reinterpret_cast<T*>(at->base + from / 8);
 }
 
 __device__ __forceinline__ uint64_t pc_uniform(uint64_t v) {
@@ -236,6 +264,92 @@ __device__ __forceinline__ void pc_tile_fill(const NodeRef* __restrict__ nodes, 
   for (int j = tid; j < n_nodes; j += kThreads) w.s_cur[j] += w.s_pre[j + 1] - w.s_pre[j];
 }
 
+// A slot of the complete table, taken: its key and row if it is occupied, and the slot left empty for the next tile.
+struct Slot { bool occ; unsigned long long key; uint64_t r0, r1; };  // (r0, r1: zero where the slot was empty)
+__device__ __forceinline__ Slot pc_take(const TileWalk& w, int slot) {
+  Slot s{w.t_key[slot] != kEmpty, w.t_key[slot], 0, 0};
+  if (s.occ) {
+    s.r0 = w.t_row[2 * slot];
+    s.r1 = w.t_row[2 * slot + 1];
+    w.t_key[slot] = kEmpty;
+    w.t_row[2 * slot] = w.t_row[2 * slot + 1] = 0;
+  }
+  return s;
+}
+
+// What a kernel of the walk is given besides its consumer's own arguments (walk_launch fills it).
+struct WalkArgs {
+  const NodeRef* nodes;
+  int n_nodes;
+  const uint64_t* proj;
+  int64_t nb;
+  int key_bits;
+  int* flags;  // the index's d_flags: [1] is set by the walk when a bucket is cut by key range
+};
+
+enum class Bucket { kWalk, kSkip, kStop };
+
+// The walk of a persistent workgroup: buckets blockIdx.x, blockIdx.x + gridDim.x, ..., each tile after tile.  A
+// kernel of the walk is `pc_walk<KeyT>(a, c)` and nothing else: its consumer c travels as a kernel argument (what
+// the host gives it first, then its LDS pointers and its state, which the device sets).  Every barrier of the
+// walk is in this function or in the three steps it calls (pc_bucket_begin: two; pc_tile_cut: three for a bucket
+// that fits a tile, otherwise two and three per halving of d; pc_tile_fill: one).  Consumer c's hooks, all called
+// by every thread, and what lies round each:
+//   c.bind(w, own)       takes its LDS arrays behind the walk's with pc_own, in the order its byte count lists
+//                        them.  The driver zeroes exactly the bytes taken; behind that: barrier [A].
+//   c.bucket_next(b)     before bucket b is begun.  Before it: [A], or the closing barrier [D] of the last tile
+//                        walked.  Behind it: the two barriers of pc_bucket_begin, then bucket_begun.
+//   c.bucket_begun(b, n) n = the bucket's entries, uniform.  Answers (uniformly) kWalk, kSkip (next bucket) or
+//                        kStop (no more buckets: finish follows).  After kWalk with n > 0 at least one tile, and
+//                        so at least five barriers, is passed before bucket_done and the next bucket_next.
+//   c.settle(flags)      between a tile's cut and its fill; uniform.  Before it: the barriers of pc_tile_cut (at
+//                        least three) and with them [D] of the tile before.  The consumer flushes or spills what
+//                        it deferred, sets its route flag and answers whether it did; if so, and only then, [B] follows.
+//   c.slot(s)            for each slot this thread takes (kSlots / kThreads rounds, slot = round * kThreads +
+//                        thread: a wave takes 64 neighbours), in every lane of every round, so wave ballots are
+//                        safe.  Before it: the barrier [C] inside pc_tile_fill: the table is complete.  Behind
+//                        the last round: the tile's closing barrier [D].
+//   c.tile_done(total)   behind [D]: what the slot rounds wrote is complete; total = the tile's entries, uniform.
+//                        Before the next slot round of any thread lie the barriers of the next cut and [C].
+//   c.bucket_done(b)     behind [D] of the bucket's last tile (or, for a bucket of no entries that was not
+//                        skipped, behind pc_bucket_begin).  No barrier before bucket_next.
+//   c.finish()           after the last bucket or kStop.  Before it: [D] of the last tile walked, or [A] if none
+//                        was.  No barrier behind it.
+// Per tile a workgroup passes: cut (3, or 2 + 3 per halving round) + [B] if settle answered true + [C] + [D],
+// i.e. five for a bucket that fits a tile; per bucket two more for pc_bucket_begin.  Barriers inside a hook are
+// the consumer's own and come on top.
+template <typename KeyT, typename Consumer>
+__device__ __forceinline__ void pc_walk(const WalkArgs& a, Consumer& c) {
+  extern __shared__ unsigned long long pc_lds[];
+  OwnLds own;
+  const TileWalk w = walk_bind(pc_lds, a.n_nodes, &own);
+  c.bind(w, &own);
+  pc_table_clear(w);
+  uint32_t* const zero = reinterpret_cast<uint32_t*>(own.base);  // (every element is 4 or 8 bytes wide)
+  for (size_t t = threadIdx.x; t < own.bytes / 4; t += kThreads) zero[t] = 0;
+  __syncthreads();  // [A]
+  const uint64_t key_max = (uint64_t(1) << a.key_bits) - 1;
+  for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
+    c.bucket_next(b);
+    int64_t left = pc_bucket_begin(a.nodes, a.n_nodes, b, w);  // entries of the bucket not yet consumed
+    const Bucket what = c.bucket_begun(b, left);
+    if (what == Bucket::kStop) break;
+    if (what == Bucket::kSkip) continue;
+    bool cut = false;
+    while (left > 0) {
+      const int total = pc_tile_cut<KeyT>(a.nodes, a.n_nodes, w, left, key_max, &cut, a.flags);
+      if (c.settle(a.flags)) __syncthreads();  // [B]
+      pc_tile_fill<KeyT>(a.nodes, a.n_nodes, a.proj, w, total);  // [C] inside
+      for (int slot = threadIdx.x; slot < kSlots; slot += kThreads) c.slot(pc_take(w, slot));
+      __syncthreads();  // [D]
+      c.tile_done(total);
+      left -= total;
+    }
+    c.bucket_done(b);
+  }
+  c.finish();
+}
+
 }  // namespace pc
 
 // Pinned words for the read-back of a call's results (the pair batch's buffer: every call that uses it has
@@ -253,10 +367,37 @@ inline int pinned_words(ksh_ctx* ctx, size_t n, int64_t** out) {
   return KSH_OK;
 }
 
-// proj[2 j], proj[2 j + 1] = anc[j] projected onto the n_cols columns of `cols`, for every node j, enqueued on the
-// context's stream (ksh_paircounts.hip).  cols travel as a kernel argument: nothing of the caller's is read after
-// the call returns.
-int pair_project(ksh_ctx* ctx, const IndexShape& x, const pc::ColList& cols, int n_cols, uint64_t* proj);
+// The host side of the three calls (ksh_rowtile.hip).
+
+// n_cols of a given column list: [1, kMaxCols].  Needs no index, so each entry point asks it before it
+// dereferences its index; `name` is what the caller calls the list ("cols", "sel->cols").
+int check_col_count(const int32_t* cols, int32_t n_cols, const char* name);
+// The columns of a call whose count has passed check_col_count: cols == NULL is all nodes in order (refused above
+// kMaxCols nodes), otherwise n_cols ids, each in [0, n_nodes) and none repeated.  *n_out = their number; col_of (if asked for) = per node its column or -1.
+int resolve_cols(const int32_t* cols, int32_t n_cols, const IndexShape& x, const char* name, pc::ColList* list,
+                 int* n_out, std::vector<int>* col_of = nullptr);
+
+// What every call starts with: the context's device, proj from the pool (16 bytes per node), the index's route
+// bits and d_flags cleared, proj formed (pair_project: proj[2 j], proj[2 j + 1] = anc[j] projected onto the n_cols
+// columns, on the context's stream; cols travel as a kernel argument, so nothing of the caller's is read after the
+// call returns).
+int walk_prologue(ksh_kss_index* idx, const IndexShape& x, const pc::ColList& cols, int n_cols, pc::PoolBuf* proj);
+
+// The grid of a walk whose workgroups take `lds` bytes: min(2 per CU by LDS, buckets, ceil(total_keys /
+// kRowsPerGroup)), at least 1.  A kernel that can ask for more than the 64 KB it gets without asking (lds_max, its
+// bytes at kMaxNodes) is granted lds_max once per context; opt_in is its bit of ksh_ctx::lds_opt_in.
+int walk_grid(ksh_ctx* ctx, const IndexShape& x, const void* kernel, size_t lds, size_t lds_max, uint32_t opt_in,
+              unsigned* grid);
+template <typename Consumer>
+int walk_launch(ksh_ctx* ctx, const IndexShape& x, const uint64_t* proj, void (*kernel)(pc::WalkArgs, Consumer),
+                size_t lds, size_t lds_max, uint32_t opt_in, const Consumer& c) {
+  unsigned grid = 0;
+  KSH_TRY(walk_grid(ctx, x, reinterpret_cast<const void*>(kernel), lds, lds_max, opt_in, &grid));
+  const pc::WalkArgs a{x.d_nodes, x.n_nodes, proj, n_buckets(&x.g), key_bits(&x.g), x.d_flags};
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(pc::kThreads), lds, ctx->stream, a, c);
+  KSH_HIP(hipGetLastError());
+  return KSH_OK;
+}
 
 }  // namespace ksh
 

@@ -32,131 +32,123 @@ constexpr int kSpecSlots = kMaxCols + 2;  // c(q) = 0 .. 128, padded to an even 
 constexpr int kAccWords = 2 + kSpecSlots;
 
 // LDS of k_select: the walk, the tile's selected keys, the spectrum counters, the number of selected keys.
-size_t select_lds_bytes(int n_nodes) { return walk_lds_bytes(n_nodes) + size_t(kTile) * 8 + size_t(kSpecSlots) * 8 + 8; }
+constexpr size_t select_lds_bytes(int n_nodes) {
+  return walk_lds_bytes(n_nodes) + size_t(kTile) * 8 + size_t(kSpecSlots) * 8 + 8;
+}
+static_assert(select_lds_bytes(kMaxNodes) == 50272 && select_lds_bytes(kMaxNodes) <= (64u << 10),
+              "49 KiB at 1024 nodes: under the 64 KB a kernel gets without asking");
 
 }  // namespace
 
 namespace ksh {
 
-// acc: see kAccWords.  kKeys == false: bucket_cnt (may be nullptr) receives each non-empty bucket's selected count
-// (the caller zeroes it), spectrum != 0 asks for acc[2 ..].  kKeys == true: offsets, out, cap.
+// The selecting consumer of the walk, in its two passes.  acc: see kAccWords.  kKeys == false: bucket_cnt (may be
+// nullptr) receives each non-empty bucket's selected count (the caller zeroes it), spectrum != 0 asks for acc[2 ..].
+// kKeys == true: offsets, out, cap.
 template <typename KeyT, bool kKeys>
-__global__ __launch_bounds__(kThreads) void k_select(const NodeRef* __restrict__ nodes, int n_nodes,
-                                                     const uint64_t* __restrict__ proj, int64_t nb, int key_bits,
-                                                     SelParams p, int spectrum, int64_t* __restrict__ bucket_cnt,
-                                                     const int64_t* __restrict__ offsets, KeyT* __restrict__ out,
-                                                     int64_t cap, unsigned long long* __restrict__ acc,
-                                                     int* __restrict__ flags) {
-  extern __shared__ unsigned long long sel_lds[];
-  unsigned long long* t_key = sel_lds;
-  unsigned long long* t_row = t_key + kSlots;
-  unsigned long long* s_sort = t_row + 2 * kSlots;
-  unsigned long long* s_spec = s_sort + kTile;
-  long long* s_cur = reinterpret_cast<long long*>(s_spec + kSpecSlots);
-  long long* s_end = s_cur + n_nodes;
-  unsigned long long* s_red = reinterpret_cast<unsigned long long*>(s_end + n_nodes);
-  int* s_n = reinterpret_cast<int*>(s_red + 8);
-  int* s_pre = s_n + 2;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const TileWalk w{t_key, t_row, s_cur, s_end, s_red, s_pre};
-  pc_table_clear(w);
-  for (int t = tid; t < kSpecSlots; t += kThreads) s_spec[t] = 0;
-  if (tid == 0) *s_n = 0;
-  __syncthreads();
-
-  const uint64_t key_max = (uint64_t(1) << key_bits) - 1;
+struct SelectConsumer {
+  SelParams p;
+  int spectrum;
+  int64_t* bucket_cnt;
+  const int64_t* offsets;
+  KeyT* out;
+  int64_t cap;
+  unsigned long long* acc;
+  unsigned long long* s_red = nullptr;   // LDS: the walk's reduction words
+  unsigned long long* s_sort = nullptr;  // LDS: kTile keys, the selected keys of a tile
+  unsigned long long* s_spec = nullptr;  // LDS: kSpecSlots counters
+  int* s_n = nullptr;                    // LDS: keys in s_sort
   int64_t grand = 0;  // (thread 0) selected k-mers of this workgroup's buckets; buckets that missed their offsets
+  int64_t my_sel = 0;               // count: what this thread selected in the bucket
+  int64_t o0 = 0, o1 = 0, run = 0;  // keys: the bucket's range and the keys stored so far
 
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    int64_t left = pc_bucket_begin(nodes, n_nodes, b, w);
-    if (left == 0 && !kKeys) continue;  // (uniform; its count stays zero)
-    int64_t o0 = 0, o1 = 0, run = 0;    // keys: the bucket's range and the keys stored so far
+  __device__ __forceinline__ void bind(const TileWalk& w, OwnLds* own) {
+    s_red = w.s_red;
+    s_sort = pc_own<unsigned long long>(own, kTile);
+    s_spec = pc_own<unsigned long long>(own, kSpecSlots);
+    s_n = pc_own<int>(own, 2);
+  }
+  __device__ __forceinline__ void bucket_next(int64_t) {}
+  __device__ __forceinline__ Bucket bucket_begun(int64_t b, int64_t left) {
+    if (left == 0 && !kKeys) return Bucket::kSkip;  // (its count stays zero)
+    my_sel = run = 0;
     if (kKeys) {
       o0 = offsets[b];
       o1 = offsets[b + 1];
     }
-    int64_t my_sel = 0;
-    bool cut = false;
-    while (left > 0) {
-      const int total = pc_tile_cut<KeyT>(nodes, n_nodes, w, left, key_max, &cut, flags);
-      pc_tile_fill<KeyT>(nodes, n_nodes, proj, w, total);
-
-      // a lane takes a slot, judges it and leaves it empty
-      for (int slot = tid; slot < kSlots; slot += kThreads) {
-        const unsigned long long key = t_key[slot];
-        const bool occ = key != kEmpty;
-        bool sel = false;
-        int m = 0;
-        if (occ) {
-          const uint64_t r0 = t_row[2 * slot], r1 = t_row[2 * slot + 1];
-          t_key[slot] = kEmpty;
-          t_row[2 * slot] = 0;
-          t_row[2 * slot + 1] = 0;
-          m = __popcll(r0) + __popcll(r1);
-          sel = m >= p.min_count && m <= p.max_count && (r0 & p.require[0]) == p.require[0] &&
-                (r1 & p.require[1]) == p.require[1] && ((r0 & p.exclude[0]) | (r1 & p.exclude[1])) == 0;
-        }
-        if (!kKeys) {
-          my_sel += sel ? 1 : 0;
-          if (spectrum) {  // one LDS add per wave and distinct multiplicity
-            unsigned long long todo = __ballot(occ);
-            while (todo) {
-              const int leader = __ffsll(todo) - 1;
-              const int mm = __shfl(m, leader, 64);
-              const unsigned long long same = __ballot(occ && m == mm);
-              if (lane == leader) atomicAdd(&s_spec[mm], static_cast<unsigned long long>(__popcll(same)));
-              todo &= ~same;
-            }
-          }
-        } else {
-          const unsigned long long chosen = __ballot(sel);
-          if (chosen) {
-            const int leader = __ffsll(chosen) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(s_n, __popcll(chosen));
-            base = __shfl(base, leader, 64);
-            const int at = base + __popcll(chosen & ((1ull << lane) - 1));
-            if (sel && at < kTile) s_sort[at] = key;  // (a tile has at most kTile distinct keys)
-          }
-        }
-      }
-      __syncthreads();
-
-      if (kKeys) {
-        const int n_sel = min(*s_n, kTile);
-        if (n_sel > 1) {
-          int width = 2;
-          while (width < n_sel) width <<= 1;
-          for (int t = n_sel + tid; t < width; t += kThreads) s_sort[t] = kEmpty;  // (above every key)
-          __syncthreads();
-          for (int k = 2; k <= width; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-              for (int t = tid; t < (width >> 1); t += kThreads) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const unsigned long long x = s_sort[i], y = s_sort[l];
-                if ((x > y) == ((i & k) == 0)) {
-                  s_sort[i] = y;
-                  s_sort[l] = x;
-                }
-              }
-              __syncthreads();
-            }
-          }
-        }
-        for (int t = tid; t < n_sel; t += kThreads) {
-          const int64_t at = o0 + run + t;
-          if (at >= o0 && at < o1 && at >= 0 && at < cap) out[at] = static_cast<KeyT>(s_sort[t]);
-        }
-        run += n_sel;
-        __syncthreads();
-        if (tid == 0) *s_n = 0;  // (read again only after the barriers of the next tile's cut and fill)
-      }
-      left -= total;
+    return Bucket::kWalk;
+  }
+  __device__ __forceinline__ bool settle(int*) { return false; }
+  // a lane judges its slot
+  __device__ __forceinline__ void slot(const Slot& s) {
+    const int lane = threadIdx.x & 63;
+    bool sel = false;
+    int m = 0;
+    if (s.occ) {
+      m = __popcll(s.r0) + __popcll(s.r1);
+      sel = m >= p.min_count && m <= p.max_count && (s.r0 & p.require[0]) == p.require[0] &&
+            (s.r1 & p.require[1]) == p.require[1] && ((s.r0 & p.exclude[0]) | (s.r1 & p.exclude[1])) == 0;
     }
     if (!kKeys) {
+      my_sel += sel ? 1 : 0;
+      if (spectrum) {  // one LDS add per wave and distinct multiplicity
+        unsigned long long todo = __ballot(s.occ);
+        while (todo) {
+          const int leader = __ffsll(todo) - 1;
+          const int mm = __shfl(m, leader, 64);
+          const unsigned long long same = __ballot(s.occ && m == mm);
+          if (lane == leader) atomicAdd(&s_spec[mm], static_cast<unsigned long long>(__popcll(same)));
+          todo &= ~same;
+        }
+      }
+    } else {
+      const unsigned long long chosen = __ballot(sel);
+      if (chosen) {
+        const int leader = __ffsll(chosen) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(s_n, __popcll(chosen));
+        base = __shfl(base, leader, 64);
+        const int at = base + __popcll(chosen & ((1ull << lane) - 1));
+        if (sel && at < kTile) s_sort[at] = s.key;  // (a tile has at most kTile distinct keys)
+      }
+    }
+  }
+  // keys: the tile's selected keys in ascending order (bitonic, barriers of its own) to their place in the bucket
+  __device__ __forceinline__ void tile_done(int) {
+    if (!kKeys) return;
+    const int tid = threadIdx.x;
+    const int n_sel = min(*s_n, kTile);
+    if (n_sel > 1) {
+      int width = 2;
+      while (width < n_sel) width <<= 1;
+      for (int t = n_sel + tid; t < width; t += kThreads) s_sort[t] = kEmpty;  // (above every key)
+      __syncthreads();
+      for (int k = 2; k <= width; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+          for (int t = tid; t < (width >> 1); t += kThreads) {
+            const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+            const unsigned long long x = s_sort[i], y = s_sort[l];
+            if ((x > y) == ((i & k) == 0)) {
+              s_sort[i] = y;
+              s_sort[l] = x;
+            }
+          }
+          __syncthreads();
+        }
+      }
+    }
+    for (int t = tid; t < n_sel; t += kThreads) {
+      const int64_t at = o0 + run + t;
+      if (at >= o0 && at < o1 && at >= 0 && at < cap) out[at] = static_cast<KeyT>(s_sort[t]);
+    }
+    run += n_sel;
+    __syncthreads();            // (every thread has read *s_n and its keys)
+    if (tid == 0) *s_n = 0;     // (added to again in a slot round: behind the barriers of the next cut and fill)
+  }
+  __device__ __forceinline__ void bucket_done(int64_t b) {
+    if (!kKeys) {
       const int64_t n_bucket = pc_block_sum(my_sel, s_red);
-      if (tid == 0) {
+      if (threadIdx.x == 0) {
         if (bucket_cnt) bucket_cnt[b] = n_bucket;
         grand += n_bucket;
       }
@@ -164,40 +156,31 @@ __global__ __launch_bounds__(kThreads) void k_select(const NodeRef* __restrict__
       grand += 1;
     }
   }
-  if (tid == 0 && grand) atomicAdd(&acc[kKeys ? 1 : 0], static_cast<unsigned long long>(grand));
-  if (!kKeys && spectrum) {
-    __syncthreads();
-    for (int t = tid; t < kSpecSlots; t += kThreads)
-      if (s_spec[t]) atomicAdd(&acc[2 + t], s_spec[t]);
+  __device__ __forceinline__ void finish() {
+    if (threadIdx.x == 0 && grand) atomicAdd(&acc[kKeys ? 1 : 0], static_cast<unsigned long long>(grand));
+    if (!kKeys && spectrum) {
+      __syncthreads();  // (a barrier of its own: in count mode the last barrier was a bucket's block sum at best)
+      for (int t = threadIdx.x; t < kSpecSlots; t += kThreads)
+        if (s_spec[t]) atomicAdd(&acc[2 + t], s_spec[t]);
+    }
   }
-}
+};
 
 template <typename KeyT, bool kKeys>
-static int launch_select(ksh_ctx* ctx, const IndexShape& x, const uint64_t* proj, const SelParams& p, int spectrum,
-                         int64_t* bucket_cnt, const int64_t* offsets, void* out, int64_t cap,
+__global__ __launch_bounds__(kThreads) void k_select(WalkArgs a, SelectConsumer<KeyT, kKeys> c) {
+  pc_walk<KeyT>(a, c);
+}
+
+template <typename KeyT>
+static int launch_select(ksh_ctx* ctx, const IndexShape& x, const uint64_t* proj, bool keys, const SelParams& p,
+                         int spectrum, int64_t* bucket_cnt, const int64_t* offsets, void* out, int64_t cap,
                          unsigned long long* acc) {
-  const size_t lds = select_lds_bytes(x.n_nodes);  // at most 54 KB (1024 nodes): no opt-in needed
-  int n_cu = 0;
-  KSH_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  const int64_t nb = n_buckets(&x.g);
-  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, int64_t(160 << 10) / int64_t(lds)));
-  const int64_t want = (x.total_keys + kRowsPerGroup - 1) / kRowsPerGroup;
-  const int64_t grid = std::max<int64_t>(1, std::min({want, nb, per_cu * n_cu}));
-  hipLaunchKernelGGL((k_select<KeyT, kKeys>), dim3(unsigned(grid)), dim3(kThreads), lds, ctx->stream,
-                     static_cast<const NodeRef*>(x.d_nodes), x.n_nodes, proj, nb, key_bits(&x.g), p, spectrum,
-                     bucket_cnt, offsets, static_cast<KeyT*>(out), cap, acc, x.d_flags);
-  KSH_HIP(hipGetLastError());
-  return KSH_OK;
-}
-template <typename KeyT>
-static int launch_count(ksh_ctx* ctx, const IndexShape& x, const uint64_t* proj, const SelParams& p, int spectrum,
-                        int64_t* bucket_cnt, unsigned long long* acc) {
-  return launch_select<KeyT, false>(ctx, x, proj, p, spectrum, bucket_cnt, nullptr, nullptr, 0, acc);
-}
-template <typename KeyT>
-static int launch_keys(ksh_ctx* ctx, const IndexShape& x, const uint64_t* proj, const SelParams& p,
-                       const int64_t* offsets, void* out, int64_t cap, unsigned long long* acc) {
-  return launch_select<KeyT, true>(ctx, x, proj, p, 0, nullptr, offsets, out, cap, acc);
+  const size_t lds = select_lds_bytes(x.n_nodes), lds_max = select_lds_bytes(kMaxNodes);
+  if (!keys)
+    return walk_launch(ctx, x, proj, k_select<KeyT, false>, lds, lds_max, 0,
+                       SelectConsumer<KeyT, false>{p, spectrum, bucket_cnt, offsets, static_cast<KeyT*>(out), cap, acc});
+  return walk_launch(ctx, x, proj, k_select<KeyT, true>, lds, lds_max, 0,
+                     SelectConsumer<KeyT, true>{p, spectrum, bucket_cnt, offsets, static_cast<KeyT*>(out), cap, acc});
 }
 
 // What does not need the index: refused before it is dereferenced.
@@ -208,8 +191,7 @@ static int check_request(const ksh_kss_selection* sel, const ksh_kss_index* idx)
   if (sel->struct_size < kMinSize)
     return fail(KSH_INVALID_ARGUMENT, "sel->struct_size = %zu is smaller than the struct up to n_exclude (%zu)",
                 sel->struct_size, kMinSize);
-  if (sel->cols && (sel->n_cols < 1 || sel->n_cols > kMaxCols))
-    return fail(KSH_INVALID_ARGUMENT, "sel->n_cols = %d is outside [1, %d]", sel->n_cols, kMaxCols);
+  KSH_TRY(check_col_count(sel->cols, sel->n_cols, "sel->cols"));
   if (sel->min_count < 1) return fail(KSH_INVALID_ARGUMENT, "sel->min_count = %d is below 1", sel->min_count);
   if (sel->max_count < 0) return fail(KSH_INVALID_ARGUMENT, "sel->max_count = %d is negative", sel->max_count);
   if (sel->max_count != 0 && sel->max_count < sel->min_count)
@@ -226,24 +208,8 @@ static int check_request(const ksh_kss_selection* sel, const ksh_kss_index* idx)
 // What reads the index's host fields: the columns, the two masks and the thresholds of a checked request.
 static int resolve_request(const ksh_kss_selection* sel, const IndexShape& x, ColList* list, int* n_cols,
                            SelParams* p) {
-  std::vector<int> col_of(size_t(x.n_nodes), -1);
-  if (!sel->cols) {
-    if (x.n_nodes > kMaxCols)
-      return fail(KSH_INVALID_ARGUMENT, "sel->cols is NULL (all nodes) but the index has %d nodes, more than %d "
-                                        "columns: name the columns of each call", x.n_nodes, kMaxCols);
-    *n_cols = x.n_nodes;
-    for (int32_t c = 0; c < *n_cols; c++) list->id[c] = col_of[size_t(c)] = c;
-  } else {
-    *n_cols = sel->n_cols;
-    for (int32_t c = 0; c < *n_cols; c++) {
-      const int32_t id = sel->cols[c];
-      if (id < 0 || id >= x.n_nodes)
-        return fail(KSH_INVALID_ARGUMENT, "sel->cols[%d] = %d is outside [0, %d)", c, id, x.n_nodes);
-      if (col_of[size_t(id)] >= 0) return fail(KSH_INVALID_ARGUMENT, "sel->cols[%d] = %d is repeated", c, id);
-      col_of[size_t(id)] = c;
-      list->id[c] = id;
-    }
-  }
+  std::vector<int> col_of;
+  KSH_TRY(resolve_cols(sel->cols, sel->n_cols, x, "sel->cols", list, n_cols, &col_of));
   if (sel->max_count > *n_cols)
     return fail(KSH_INVALID_ARGUMENT, "sel->max_count = %d is above n_cols = %d", sel->max_count, *n_cols);
   if (sel->min_count > *n_cols)
@@ -268,19 +234,6 @@ static int resolve_request(const ksh_kss_selection* sel, const IndexShape& x, Co
   return KSH_OK;
 }
 
-// The walk both calls start with: route bits cleared, results zeroed, proj formed.
-static int begin_pass(ksh_kss_index* idx, const IndexShape& x, const ColList& list, int n_cols, PoolBuf* proj,
-                      PoolBuf* acc) {
-  ksh_ctx* ctx = x.ctx;
-  KSH_HIP(hipSetDevice(ctx->device));
-  KSH_TRY(pool_alloc(ctx, size_t(x.n_nodes) * 16, &proj->p));
-  KSH_TRY(pool_alloc(ctx, size_t(kAccWords) * 8, &acc->p));
-  index_set_routes(idx, 0);
-  KSH_HIP(hipMemsetAsync(x.d_flags, 0, 16, ctx->stream));
-  KSH_HIP(hipMemsetAsync(acc->p, 0, size_t(kAccWords) * 8, ctx->stream));
-  return pair_project(ctx, x, list, n_cols, static_cast<uint64_t*>(proj->p));
-}
-
 }  // namespace ksh
 
 using namespace ksh;
@@ -297,12 +250,14 @@ extern "C" int ksh_kss_select_count(const ksh_kss_selection* sel, ksh_kss_index*
   KSH_TRY(resolve_request(sel, x, &list, &n_cols, &p));
   ksh_ctx* ctx = x.ctx;
   PoolBuf proj(ctx), acc(ctx);
-  KSH_TRY(begin_pass(idx, x, list, n_cols, &proj, &acc));
+  KSH_TRY(walk_prologue(idx, x, list, n_cols, &proj));
+  KSH_TRY(pool_alloc(ctx, size_t(kAccWords) * 8, &acc.p));
+  KSH_HIP(hipMemsetAsync(acc.p, 0, size_t(kAccWords) * 8, ctx->stream));
   const int64_t nb = n_buckets(&x.g);
   if (d_offsets) KSH_HIP(hipMemsetAsync(d_offsets, 0, size_t(nb + 1) * 8, ctx->stream));
   auto* d_acc = static_cast<unsigned long long*>(acc.p);
-  KSH_TRY(KSH_BY_KEY(x.g.key_bytes, launch_count, ctx, x, static_cast<const uint64_t*>(proj.p), p,
-                     spectrum ? 1 : 0, d_offsets, d_acc));
+  KSH_TRY(KSH_BY_KEY(x.g.key_bytes, launch_select, ctx, x, static_cast<const uint64_t*>(proj.p), false, p,
+                     spectrum ? 1 : 0, d_offsets, nullptr, nullptr, 0, d_acc));
   if (d_offsets) {
     KSH_TRY(arena_reserve(ctx, size_t(nb / 256 + 1024) * 16));  // (the block sums of a scan of many buckets)
     arena_reset(ctx);
@@ -331,10 +286,12 @@ extern "C" int ksh_kss_select_keys(const ksh_kss_selection* sel, ksh_kss_index* 
   KSH_TRY(resolve_request(sel, x, &list, &n_cols, &p));
   ksh_ctx* ctx = x.ctx;
   PoolBuf proj(ctx), acc(ctx);
-  KSH_TRY(begin_pass(idx, x, list, n_cols, &proj, &acc));
+  KSH_TRY(walk_prologue(idx, x, list, n_cols, &proj));
+  KSH_TRY(pool_alloc(ctx, size_t(kAccWords) * 8, &acc.p));
+  KSH_HIP(hipMemsetAsync(acc.p, 0, size_t(kAccWords) * 8, ctx->stream));
   auto* d_acc = static_cast<unsigned long long*>(acc.p);
-  KSH_TRY(KSH_BY_KEY(x.g.key_bytes, launch_keys, ctx, x, static_cast<const uint64_t*>(proj.p), p, d_offsets, d_keys,
-                     n_keys, d_acc));
+  KSH_TRY(KSH_BY_KEY(x.g.key_bytes, launch_select, ctx, x, static_cast<const uint64_t*>(proj.p), true, p, 0, nullptr,
+                     d_offsets, d_keys, n_keys, d_acc));
   KSH_HIP(hipMemcpyAsync(ctx->h_pinned, d_acc, 16, hipMemcpyDeviceToHost, ctx->stream));
   KSH_HIP(hipStreamSynchronize(ctx->stream));
   if (ctx->h_pinned[1] != 0)

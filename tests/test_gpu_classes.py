@@ -314,7 +314,8 @@ def test_refusals_that_read_the_index(two_words):
     idx, gets, every, own = two_words
     serve = want_classes(gets, every, [7, 63])
     for bad, word in ((dict(cols=None), "131 nodes"), (dict(cols=[0, 131]), "outside"), (dict(cols=[-1]), "outside"),
-                      (dict(cols=[5, 9, 5]), "repeated")):
+                      (dict(cols=[5, 9, 5]), "repeated"), (dict(cols=list(range(129))), "n_cols"),
+                      (dict(cols=[]), "n_cols")):
         with pytest.raises(capi.KshError) as e:
             idx.color_classes(**bad)
         assert e.value.code == capi.KSH_INVALID_ARGUMENT and word in str(e.value), bad

@@ -276,7 +276,8 @@ def test_column_words(ctx):
 
     serve = want_selection(gets, [7, 3], require=[3])
     for bad, word in ((dict(cols=None), "130 nodes"), (dict(cols=[0, 130]), "outside"), (dict(cols=[-1]), "outside"),
-                      (dict(cols=[5, 9, 5]), "repeated"), (dict(cols=[5, 9], require=[130]), "outside"),
+                      (dict(cols=[5, 9, 5]), "repeated"), (dict(cols=list(range(129))), "n_cols"),
+                      (dict(cols=[]), "n_cols"), (dict(cols=[5, 9], require=[130]), "outside"),
                       (dict(cols=[5, 9], require=[7]), "not in cols"), (dict(cols=[5, 9], exclude=[7]), "not in cols"),
                       (dict(cols=[5, 9], require=[9], exclude=[9]), "both"),
                       (dict(cols=[5, 9], max_count=3), "max_count"), (dict(cols=[5, 9], min_count=3), "min_count")):
