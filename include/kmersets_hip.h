@@ -168,7 +168,7 @@ int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
  * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
  * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
  * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
- * ksh_kss_select_keys, ksh_kss_color_classes and the accessors of a ksh_kss /
+ * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes and the accessors of a ksh_kss /
  * ksh_kss_index, plans and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
  * plan: nothing else uses their slot.
  *
@@ -620,7 +620,7 @@ int ksh_kss_index_query(ksh_kss_index* idx, const uint64_t* d_kmers, int64_t n, 
 int ksh_kss_index_info(const ksh_kss_index* idx, int32_t* n_nodes, int32_t* words_per_row,
                        int64_t* resident_bytes);
 /* The routes the last query (ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
- * ksh_kss_select_keys or ksh_kss_color_classes) took, a mask of KSH_QROUTE_* (synchronises the stream). */
+ * ksh_kss_select_keys, ksh_kss_select_class_ids or ksh_kss_color_classes) took, a mask of KSH_QROUTE_* (synchronises the stream). */
 enum {
   KSH_QROUTE_SEARCH = 1 << 0,    /* per-query search                                            */
   KSH_QROUTE_JOIN = 1 << 1,      /* bucket join                                                  */
@@ -629,7 +629,8 @@ enum {
   KSH_QROUTE_SEQ_PASSES = 1 << 4, /* ksh_seq_hits: the batch took more than one pass of positions */
   KSH_QROUTE_PAIR_SPLIT = 1 << 5, /* ksh_kss_pair_counts, ksh_kss_select_count, ksh_kss_select_keys: some bucket's
                                      k-mers did not fit one tile and were cut by key range (ksh_kss_color_classes
-                                     reports it with the same meaning)                            */
+                                     reports it with the same meaning, and so does
+                                     ksh_kss_select_class_ids)                                    */
   KSH_QROUTE_PAIR_FLUSH = 1 << 6, /* ... some workgroup flushed its counters before its last tile */
   KSH_QROUTE_CLASS_SPILL = 1 << 7 /* ksh_kss_color_classes: some workgroup emptied its on-chip class table into
                                      the global one before its last tile                          */
@@ -775,6 +776,42 @@ int ksh_kss_select_keys(const ksh_kss_selection* sel, ksh_kss_index* idx, const 
  * last call.  The index must be usable as for ksh_kss_index_query. */
 int ksh_kss_color_classes(const int32_t* cols, int32_t n_cols, ksh_kss_index* idx, int64_t capacity, uint64_t* rows,
                           int64_t* counts, int64_t* n_classes);
+
+/* ---- The colour class of every selected k-mer: a coloured-graph export ---------------------------------------
+ * ksh_kss_select_keys with, beside every key, the position of the k-mer's row in a class table: the union selection
+ * with the whole table of ksh_kss_color_classes over the same cols is what a coloured de Bruijn graph stores, the
+ * k-mers and one small integer per k-mer that indexes the table.
+ * sel, idx, d_offsets, n_keys, d_keys: as in ksh_kss_select_keys -- the offsets are those ksh_kss_select_count made
+ * for the same request and index, bucket b goes to d_keys[d_offsets[b] .. d_offsets[b + 1]) ascending in the index's
+ * key width, nothing is written at or beyond n_keys nor outside a bucket's own range, and a bucket that does not
+ * match its offsets gives KSH_FAILED_PRECONDITION after the call's one synchronisation.  d_keys may be NULL: only the
+ * ids are written.
+ * rows: a HOST class table of n_classes rows, uint64[2 * n_classes], 1 <= n_classes <= 2^24, in the format and order
+ * ksh_kss_color_classes returns for the same cols: rows[2 c] = the bits of columns 0..63, rows[2 c + 1] = the bits of
+ * columns 64..127, strictly ascending by (rows[2 c + 1], rows[2 c]).  It is only read during the call.  It may be the
+ * whole table or any strictly ascending subset of it -- only the one-bit classes, say, to label private k-mers by
+ * sample.
+ * d_class_ids (device, uint32[n_keys]): d_class_ids[p] is the class of the key written (or, with d_keys NULL, that
+ * would be written) at d_keys[p]: the c with rows[2 c], rows[2 c + 1] equal to that k-mer's row over sel->cols, or
+ * KSH_CLASS_NONE if the table does not hold the row.
+ * n_unmatched (host) says what a row that the table does not hold means.  NULL: any selected k-mer with such a row
+ * makes the call KSH_FAILED_PRECONDITION with a message that names rows and gives the number of such k-mers -- the
+ * table belongs to another request or index; the outputs are then unspecified within [0, n_keys).  Non-NULL: it
+ * receives that number and the call is KSH_OK.
+ * KSH_INVALID_ARGUMENT, each with a message that names the field.  Before the index is dereferenced: what
+ * ksh_kss_select_keys refuses there (but for a NULL d_keys); NULL rows; n_classes outside [1, 2^24]; NULL d_class_ids
+ * with n_keys > 0; rows that are not strictly ascending (the message gives the first offending index).  After reading
+ * only the index's host fields: what ksh_kss_select_keys refuses there; a row with a bit at or above n_cols.  The
+ * index still serves after any refusal.
+ * The call is stateless like its siblings: scratch comes from the context's pool (16 bytes per node, 16 bytes per
+ * class, 32 bytes per slot of a table of the next power of two >= 2 * n_classes slots) and is given back before the
+ * call returns; it synchronises the index's context stream once; it keeps no plan, joins no plan group and ends no
+ * pending plan.  ksh_kss_index_routes reports KSH_QROUTE_PAIR_SPLIT for the last call with the meaning it has for
+ * ksh_kss_pair_counts.  The index must be usable as for ksh_kss_index_query. */
+#define KSH_CLASS_NONE 0xFFFFFFFFu
+int ksh_kss_select_class_ids(const ksh_kss_selection* sel, ksh_kss_index* idx, const uint64_t* rows,
+                             int64_t n_classes, const int64_t* d_offsets, int64_t n_keys, void* d_keys,
+                             uint32_t* d_class_ids, int64_t* n_unmatched);
 
 #ifdef __cplusplus
 }

@@ -402,6 +402,35 @@ class KmerSetSetIndex {
     }
   }
 
+  // The selection of Select with the colour class of every k-mer (ksh_kss_select_class_ids): the set, and for the
+  // i-th k-mer of the set in ascending order -- the order of Find() -- the position in `classes` of its membership
+  // pattern over cols.  `classes` is what ColorClasses(cols) returned, or any part of it in the same order that
+  // holds the pattern of every selected k-mer; a table that misses one (that of other columns or another
+  // structure) is refused.  The union selection with the whole table is a coloured de Bruijn graph.
+  std::pair<KmerSet<K, N, KeyType>, std::vector<std::uint32_t>> SelectClasses(
+      const std::vector<int>& cols, const std::vector<ColorClass>& classes, int min_count = 1, int max_count = 0,
+      const std::vector<int>& require = {}, const std::vector<int>& exclude = {}) const {
+    using Set = KmerSet<K, N, KeyType>;
+    const std::vector<std::int32_t> ids(cols.begin(), cols.end()), req(require.begin(), require.end()),
+        exc(exclude.begin(), exclude.end());
+    const ksh_kss_selection sel = Selection(ids, min_count, max_count, req, exc);
+    std::vector<std::uint64_t> rows;
+    rows.reserve(2 * classes.size());
+    for (const ColorClass& c : classes) rows.insert(rows.end(), {c.row[0], c.row[1]});
+    ksc::DeviceBuffer off(std::size_t(Set::kBucketsNum + 1) * 8);
+    std::int64_t n = 0;
+    ksc::Check(ksh_kss_select_count(&sel, index_, static_cast<std::int64_t*>(off.get()), &n, nullptr));
+    ksc::DeviceBuffer keys(std::max<std::size_t>(std::size_t(n) * Set::kDeviceKeyBytes, 16));
+    ksc::DeviceBuffer d_ids(std::max<std::size_t>(std::size_t(n) * 4, 16));
+    if (n > 0 || !rows.empty())  // (an index without k-mers has no class, and the call takes no empty table)
+      ksc::Check(ksh_kss_select_class_ids(&sel, index_, rows.data(), static_cast<std::int64_t>(classes.size()),
+                                          static_cast<const std::int64_t*>(off.get()), n, keys.get(),
+                                          static_cast<std::uint32_t*>(d_ids.get()), nullptr));
+    std::vector<std::uint32_t> out;
+    if (n > 0) out = d_ids.ToHost<std::uint32_t>(std::size_t(n));
+    return {Set::FromDevice(std::move(off), std::move(keys), n), std::move(out)};
+  }
+
  private:
   static ksh_kss_selection Selection(const std::vector<std::int32_t>& ids, int min_count, int max_count,
                                      const std::vector<std::int32_t>& req, const std::vector<std::int32_t>& exc) {

@@ -11,9 +11,9 @@
 //              to the global table and clears its own before the next tile, and at its end what is left;
 //   global   : an open-addressing table of 2^m >= 2 * capacity slots in pool memory, packed by k_class_pack; the
 //              host sorts the packed classes.
-// Both tables take a row by the same insertion, cls_insert: three set-once words per slot, each claimed by atomicCAS
-// from 0, no lane ever waits for another, every probe loop is bounded by the table's slot count.
-#include "ksh_rowtile.h"
+// Both tables take a row by the same insertion, cls_insert (ksh_clstable.h): three set-once words per slot, each
+// claimed by atomicCAS from 0, no lane ever waits for another, every probe loop is bounded by the table's slot count.
+#include "ksh_clstable.h"
 
 #include <algorithm>
 #include <array>
@@ -25,7 +25,6 @@ namespace {
 constexpr int kClsSlots = 1024;                       // slots of a workgroup's class table
 constexpr int kClsSpill = kClsSlots * 3 / 4 - kTile;  // spill above this: the next tile's <= kTile new classes
                                                       // still fit at no more than 3/4 load
-constexpr unsigned long long kValid = 1ull << 63;     // set in every written key word: 0 is "not yet written"
 constexpr int64_t kMaxCapacity = int64_t(1) << 24;
 constexpr int64_t kFirstCopy = 4096;  // classes read back with the call's one synchronisation (more: a second copy)
 // device words of a call, in front of the packed classes: [0] slots of the global table that are taken, [1] non-zero:
@@ -42,50 +41,6 @@ static_assert(kClassesLdsMax == 77904 && 2 * kClassesLdsMax <= (160u << 10),
 }  // namespace
 
 namespace ksh {
-
-__device__ __forceinline__ uint32_t cls_hash(uint64_t r0, uint64_t r1) {
-  return uint32_t(pc_mix(r0 ^ pc_mix(r1 + 0x9E3779B97F4A7C15ull)));
-}
-
-// Adds cnt to the slot of row (r0, r1), taking an empty slot if the row has none.  Word i of slot s is
-// base[s * kStride + i * kPlane]: i = 0, 1, 2 the key, i = 3 the count.  At 128 columns every 128-bit value is a
-// row, so no row word has a value to spare for "empty" and there is no 128-bit compare-and-swap: the key is three
-// words that carry 63 bits of r0, 63 bits of r1 and the two top bits, each with kValid set, each written once, by
-// atomicCAS from 0.  A thread claims word 0; if it was 0 or is its own it claims word 1 the same way, then word 2;
-// on any other value it goes to the next slot.
-//   - Whoever writes word i of a slot goes on to word i + 1 of it, and had matched the words before i: so every
-//     slot whose word 0 is written ends with all three written, and they are the key of the thread that wrote (or
-//     first matched) word 2 -- the key of a row that was inserted, which then adds its count: no slot stays half
-//     written or with a zero count once the inserting threads are done.
-//   - A thread leaves a slot only on a word that holds another value, and words never change once written: two
-//     threads with the same row decide alike at every slot and settle on the same one.  A row has one slot.
-//   - Nobody waits for a value: a wave's lanes may insert side by side, in lockstep.
-// The loop visits every slot at most once.  Returns false when each held another row.  *claims grows by the
-// slots whose word 0 this call wrote: each is some row's new slot (not necessarily this row's).
-template <int kStride, int kPlane>
-__device__ __forceinline__ bool cls_insert(unsigned long long* base, uint32_t mask, uint64_t r0, uint64_t r1,
-                                           unsigned long long cnt, int* claims) {
-  const unsigned long long w0 = (r0 & ~kValid) | kValid, w1 = (r1 & ~kValid) | kValid;
-  const unsigned long long w2 = (r0 >> 63) | ((r1 >> 63) << 1) | kValid;
-  uint32_t h = cls_hash(r0, r1) & mask;
-  for (uint32_t probe = 0; probe <= mask; probe++, h = (h + 1) & mask) {
-    unsigned long long* s = base + size_t(h) * kStride;
-    unsigned long long prev = atomicCAS(s, 0ull, w0);
-    if (prev != 0 && prev != w0) continue;
-    if (prev == 0) *claims += 1;
-    prev = atomicCAS(s + kPlane, 0ull, w1);
-    if (prev != 0 && prev != w1) continue;
-    prev = atomicCAS(s + 2 * kPlane, 0ull, w2);
-    if (prev != 0 && prev != w2) continue;
-    atomicAdd(s + 3 * kPlane, cnt);
-    return true;
-  }
-  return false;
-}
-
-__device__ __forceinline__ unsigned long long cls_peek(const unsigned long long* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // Every entry of the workgroup's table into the global one; the table is left empty.  Called behind a tile's
 // closing barrier (the table is complete); a barrier follows before the table is inserted into again.  Once the call has failed (ctl[1]) nothing more is inserted.

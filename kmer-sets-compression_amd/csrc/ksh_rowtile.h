@@ -1,6 +1,6 @@
 // The tile walk over a KmerSetSet index that ksh_kss_pair_counts (ksh_paircounts.hip), ksh_kss_select_*
-// (ksh_select.hip) and ksh_kss_color_classes (ksh_classes.hip) share, and the host
-// side of the three calls (ksh_rowtile.hip).  gfx950 only.
+// (ksh_select.hip), ksh_kss_color_classes (ksh_classes.hip) and ksh_kss_select_class_ids (ksh_classids.hip) share
+// (DESIGN.md 3.8c - 3.8f), and the host side of these calls (ksh_rowtile.hip).  gfx950 only.
 //
 // A workgroup of kThreads walks one bucket at a time.  A bucket whose entries (all nodes together) fit a tile is
 // one tile; otherwise the workgroup walks the bucket's key range left to right and cuts it by key: every tile is
@@ -56,7 +56,7 @@ __host__ __device__ constexpr WalkLayout walk_layout(int n_nodes) {
 }
 // A consumer's launch passes walk_lds_bytes(n_nodes) + the bytes of what it takes with pc_own.
 constexpr size_t walk_lds_bytes(int n_nodes) { return walk_layout(n_nodes).own * 8; }
-constexpr int kMaxNodes = 1024;  // the node count the LDS budgets are quoted at (DESIGN.md 3.8c - 3.8e)
+constexpr int kMaxNodes = 1024;  // the node count the LDS budgets are quoted at (DESIGN.md 3.8c - 3.8f)
 static_assert(walk_lds_bytes(kMaxNodes) == 45128 && walk_lds_bytes(127) == 27184, "the walk's LDS: 24 KiB + 64 + "
               "20 bytes per node, the prefix rounded to 8");
 
@@ -367,7 +367,7 @@ inline int pinned_words(ksh_ctx* ctx, size_t n, int64_t** out) {
   return KSH_OK;
 }
 
-// The host side of the three calls (ksh_rowtile.hip).
+// The host side of the calls (ksh_rowtile.hip).
 
 // n_cols of a given column list: [1, kMaxCols].  Needs no index, so each entry point asks it before it
 // dereferences its index; `name` is what the caller calls the list ("cols", "sel->cols").

@@ -13,7 +13,7 @@
 //          running count.  Tiles of a bucket are ordered by the cut, so the bucket comes out ascending.  Every store
 //          is inside [offsets[b], offsets[b + 1]) and [0, n_keys); a bucket whose count is not
 //          offsets[b + 1] - offsets[b] is reported.
-#include "ksh_rowtile.h"
+#include "ksh_selection.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -21,11 +21,6 @@
 using namespace ksh::pc;
 
 namespace {
-
-struct SelParams {
-  uint64_t require[2], exclude[2];
-  int32_t min_count, max_count;
-};
 
 constexpr int kSpecSlots = kMaxCols + 2;  // c(q) = 0 .. 128, padded to an even count
 // device results of a call: [0] selected k-mers, [1] buckets that missed their offsets, [2 ..] the spectrum
@@ -84,11 +79,7 @@ struct SelectConsumer {
     const int lane = threadIdx.x & 63;
     bool sel = false;
     int m = 0;
-    if (s.occ) {
-      m = __popcll(s.r0) + __popcll(s.r1);
-      sel = m >= p.min_count && m <= p.max_count && (s.r0 & p.require[0]) == p.require[0] &&
-            (s.r1 & p.require[1]) == p.require[1] && ((s.r0 & p.exclude[0]) | (s.r1 & p.exclude[1])) == 0;
-    }
+    if (s.occ) sel = sel_judge(p, s.r0, s.r1, &m);
     if (!kKeys) {
       my_sel += sel ? 1 : 0;
       if (spectrum) {  // one LDS add per wave and distinct multiplicity
@@ -184,7 +175,7 @@ static int launch_select(ksh_ctx* ctx, const IndexShape& x, const uint64_t* proj
 }
 
 // What does not need the index: refused before it is dereferenced.
-static int check_request(const ksh_kss_selection* sel, const ksh_kss_index* idx) {
+int check_request(const ksh_kss_selection* sel, const ksh_kss_index* idx) {
   if (!sel) return fail(KSH_INVALID_ARGUMENT, "sel is NULL");
   if (!idx) return fail(KSH_INVALID_ARGUMENT, "idx is NULL");
   constexpr size_t kMinSize = offsetof(ksh_kss_selection, n_exclude) + sizeof(int32_t);
@@ -206,8 +197,7 @@ static int check_request(const ksh_kss_selection* sel, const ksh_kss_index* idx)
 }
 
 // What reads the index's host fields: the columns, the two masks and the thresholds of a checked request.
-static int resolve_request(const ksh_kss_selection* sel, const IndexShape& x, ColList* list, int* n_cols,
-                           SelParams* p) {
+int resolve_request(const ksh_kss_selection* sel, const IndexShape& x, ColList* list, int* n_cols, SelParams* p) {
   std::vector<int> col_of;
   KSH_TRY(resolve_cols(sel->cols, sel->n_cols, x, "sel->cols", list, n_cols, &col_of));
   if (sel->max_count > *n_cols)

@@ -195,6 +195,8 @@ def lib():
         "ksh_kss_pair_counts": (C.c_int, [C.POINTER(i32), i32, vp, i64, vp, C.POINTER(i64)]),
         "ksh_kss_select_count": (C.c_int, [C.POINTER(Selection), vp, vp, C.POINTER(i64), C.POINTER(i64)]),
         "ksh_kss_select_keys": (C.c_int, [C.POINTER(Selection), vp, vp, i64, vp]),
+        "ksh_kss_select_class_ids": (C.c_int, [C.POINTER(Selection), vp, C.POINTER(C.c_uint64), i64, vp, i64, vp, vp,
+                                               C.POINTER(i64)]),
         "ksh_kss_color_classes": (C.c_int, [C.POINTER(i32), i32, vp, i64, C.POINTER(C.c_uint64), C.POINTER(i64),
                                             C.POINTER(i64)]),
     }
@@ -1004,6 +1006,7 @@ class DeviceKmerSetSet:
 
 QROUTE_SEARCH, QROUTE_JOIN, QROUTE_OVERSIZE, QROUTE_CHUNKED, QROUTE_SEQ_PASSES = 1, 2, 4, 8, 16
 QROUTE_PAIR_SPLIT, QROUTE_PAIR_FLUSH, QROUTE_CLASS_SPILL = 32, 64, 128
+CLASS_NONE = 0xFFFFFFFF  # KSH_CLASS_NONE: the id of a k-mer whose row the class table does not hold
 
 
 class KssIndex:
@@ -1230,6 +1233,52 @@ class KssIndex:
                 check(rc)
                 del keep
                 return rows[:got.value].copy(), counts[:got.value].copy()
+
+    def select_class_ids(self, offsets, n_keys, rows, keys=None, ids=None, cols=None, min_count=1, max_count=None,
+                         require=(), exclude=(), allow_unmatched=False):
+        """ksh_kss_select_class_ids, the raw call: writes the selection's keys into `keys` (a device tensor of at
+        least n_keys keys, or None: only the ids are written) and beside each key the position of its row in the
+        class table `rows` (np.uint64[n, 2] as color_classes returns it, or an ascending subset) into `ids` (a
+        device int32 tensor of at least n_keys values, or None with n_keys == 0).  A k-mer whose row is not in the
+        table is refused, or with allow_unmatched gets CLASS_NONE (-1 as int32); the number of such k-mers is
+        returned with allow_unmatched, otherwise None."""
+        import torch
+
+        with torch.cuda.stream(self.ctx.stream):
+            h = self._handle()
+            sel, n_cols, keep = self._selection(cols, min_count, max_count, require, exclude)
+            table = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+            missing = C.c_int64()
+            check(lib().ksh_kss_select_class_ids(
+                C.byref(sel), h, table.ctypes.data_as(C.POINTER(C.c_uint64)) if table is not None else None,
+                table.size // 2 if table is not None else 0, offsets.data_ptr() if offsets is not None else None,
+                int(n_keys), keys.data_ptr() if keys is not None else None,
+                ids.data_ptr() if ids is not None else None, C.byref(missing) if allow_unmatched else None))
+            del keep
+            return missing.value if allow_unmatched else None
+
+    def select_classes(self, cols=None, min_count=1, max_count=None, require=(), exclude=(), rows=None,
+                       allow_unmatched=False):
+        """The selection of select() with the colour class of every k-mer: (DeviceSet, ids, rows, counts).  ids is a
+        device int32 tensor aligned with the set's keys: ids[p] is the position in `rows` of the membership pattern
+        of key p over cols, or -1 (CLASS_NONE) where allow_unmatched lets a pattern be absent from the table.
+        rows None: the table is color_classes(cols), returned with its counts; a given table (np.uint64[n, 2],
+        ascending as color_classes returns it, or a subset of it) is returned as it is, with counts None.  The union
+        selection with the whole table is a coloured de Bruijn graph: its k-mers, a class per k-mer, the classes."""
+        import torch
+
+        counts = None
+        if rows is None:
+            rows, counts = self.color_classes(cols)
+        off, n, _ = self.select_count(cols, min_count, max_count, require, exclude)
+        with torch.cuda.stream(self.ctx.stream):
+            keys = torch.empty(max(n * self.g.key_bytes, 16), dtype=torch.uint8, device=self.ctx.device)
+            ids = torch.empty(max(n, 1), dtype=torch.int32, device=self.ctx.device)
+        if n == 0 and len(rows) == 0:  # (an index without k-mers: no class to name, and the call takes no empty table)
+            return DeviceSet(self.g, off, keys, 0), ids[:0], rows, counts
+        self.select_class_ids(off, n, rows, keys, ids, cols, min_count, max_count, require, exclude,
+                              allow_unmatched=allow_unmatched)
+        return DeviceSet(self.g, off, keys, n), ids[:n], rows, counts
 
     @staticmethod
     def class_matrix(rows, n_cols):
