@@ -104,7 +104,8 @@ int ksh_ctx_reserve(ksh_ctx* ctx, size_t bytes);
  *        3 = SPSS encode, neighbour probe stage (partition + LDS-staged probes: the loop's dominant stage)
  *        4 = SPSS encode, chain ranking walks (k_rank_walk / k_rank_heads, or the stamping k_ruler_walk /
  *            k_ruler_heads)   5 = SPSS encode, base emit (k_emit_rulers / k_emit_heads, or k_emit)
- * ksh_ctx_timing_units: the k-mers (kinds 3..5) the timed launches of a kind covered. */
+ *        6 = ksh_seq_class_runs, extraction and look-up of a pass   7 = ..., classification and runs of a pass
+ * ksh_ctx_timing_units: the k-mers (kinds 3..5) or positions (6, 7) the timed launches of a kind covered. */
 int ksh_ctx_enable_timing(ksh_ctx* ctx, int enable);
 int ksh_ctx_timing_reset(ksh_ctx* ctx);
 int ksh_ctx_timing_read(ksh_ctx* ctx, int kind, float* total_ms, int64_t* launches);
@@ -168,7 +169,7 @@ int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
  * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
  * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
  * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
- * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes and the accessors of a ksh_kss /
+ * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes, ksh_seq_class_runs and the accessors of a ksh_kss /
  * ksh_kss_index, plans and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
  * plan: nothing else uses their slot.
  *
@@ -620,13 +621,14 @@ int ksh_kss_index_query(ksh_kss_index* idx, const uint64_t* d_kmers, int64_t n, 
 int ksh_kss_index_info(const ksh_kss_index* idx, int32_t* n_nodes, int32_t* words_per_row,
                        int64_t* resident_bytes);
 /* The routes the last query (ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
- * ksh_kss_select_keys, ksh_kss_select_class_ids or ksh_kss_color_classes) took, a mask of KSH_QROUTE_* (synchronises the stream). */
+ * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes or ksh_seq_class_runs) took, a mask of
+ * KSH_QROUTE_* (synchronises the stream). */
 enum {
   KSH_QROUTE_SEARCH = 1 << 0,    /* per-query search                                            */
   KSH_QROUTE_JOIN = 1 << 1,      /* bucket join                                                  */
   KSH_QROUTE_OVERSIZE = 1 << 2,  /* ... some node's slice outgrew the LDS stage: searched in HBM */
   KSH_QROUTE_CHUNKED = 1 << 3,   /* ... the batch took more than one pass of 2^24 queries        */
-  KSH_QROUTE_SEQ_PASSES = 1 << 4, /* ksh_seq_hits: the batch took more than one pass of positions */
+  KSH_QROUTE_SEQ_PASSES = 1 << 4, /* ksh_seq_hits, ksh_seq_class_runs: more than one pass of positions */
   KSH_QROUTE_PAIR_SPLIT = 1 << 5, /* ksh_kss_pair_counts, ksh_kss_select_count, ksh_kss_select_keys: some bucket's
                                      k-mers did not fit one tile and were cut by key range (ksh_kss_color_classes
                                      reports it with the same meaning, and so does
@@ -812,6 +814,63 @@ int ksh_kss_color_classes(const int32_t* cols, int32_t n_cols, ksh_kss_index* id
 int ksh_kss_select_class_ids(const ksh_kss_selection* sel, ksh_kss_index* idx, const uint64_t* rows,
                              int64_t n_classes, const int64_t* d_offsets, int64_t n_keys, void* d_keys,
                              uint32_t* d_class_ids, int64_t* n_unmatched);
+
+/* ---- Painting sequences with colour classes: runs of equal class per sequence ----------------------------------
+ * Which stretch of a contig, a read or a reference genome is held by which exact subset of the chosen sets.  Sequences
+ * and positions are those of ksh_seq_hits: sequence s has positions 0 .. lens[s], no window crosses from one string
+ * into the next.  The row of a position has bit a set iff its k-mer (canonicalised if asked) is in Get(cols[a]); a
+ * k-mer that no node holds has the zero row, and so has one that only nodes outside cols hold.  The class of a
+ * position is the c whose rows[2 c], rows[2 c + 1] equal its row, or KSH_CLASS_NONE if the table does not hold the
+ * row.  A run is a maximal stretch of consecutive positions of one sequence with the same class: adjacent runs of a
+ * sequence differ in class, a run never continues from one sequence into the next (even when the classes agree), and
+ * every sequence has at least one run, so n_runs >= n_strings.  Painting the strings of ksh_spss_encode of the union
+ * selection with the whole table of ksh_kss_color_classes gives the compact colouring of a coloured de Bruijn graph:
+ * one class per run of positions, not one per k-mer (DESIGN.md 3.8g has the measured ratio).
+ * Everything a ksh_seq_paint points to is HOST memory and only read during the call. */
+typedef struct ksh_seq_paint {
+  size_t struct_size;          /* sizeof(ksh_seq_paint) of the caller's header */
+  const int32_t* cols;         /* as ksh_kss_color_classes: 1..128 distinct node ids, any order, internal nodes
+                                  allowed; NULL = all nodes in order (n_cols ignored), refused above 128 nodes */
+  int32_t n_cols;
+  int32_t canonicalize;        /* as ksh_seq_hits */
+  const uint64_t* rows;        /* class table, as ksh_kss_select_class_ids: uint64[2 * n_classes], strictly */
+  int64_t n_classes;           /* ascending by (rows[2c+1], rows[2c]), 1..2^24, whole table or any subset of it */
+  int32_t route;               /* as ksh_seq_hits: 0 auto, 1 search, 2 join */
+  int64_t pass_positions;      /* as ksh_seq_hits: 0 = default */
+} ksh_seq_paint;
+/* *n_runs (host, required): the number of runs of all sequences -- always the true number, also on the capacity
+ * refusal below.
+ * d_run_offsets (device int64[n_strings + 1], may be NULL): the runs of sequence s are runs off[s] .. off[s + 1);
+ * off[n_strings] == n_runs.
+ * d_run_start, d_run_class (device uint32[capacity]): run r of sequence s begins at position d_run_start[r] of s (the
+ * first run of a sequence at 0), has class d_run_class[r], and ends before the next run of s begins, or at
+ * lens[s] + 1.  capacity == 0: count only, the two arrays may be NULL and are not touched.  capacity > 0: both are
+ * required.  n_runs > capacity > 0: KSH_FAILED_PRECONDITION with a message that names capacity and gives n_runs; the
+ * first capacity entries are then unspecified.  Nothing is ever written at or beyond capacity, whatever the inputs.
+ * n_unmatched (host) counts the POSITIONS with KSH_CLASS_NONE, and is as in ksh_kss_select_class_ids.  NULL: any such
+ * position makes the call KSH_FAILED_PRECONDITION with a message that names rows and gives their number.  Non-NULL: it
+ * receives the number and the call is KSH_OK.
+ * n_strings == 0: KSH_OK, *n_runs = 0, d_run_offsets[0] = 0 if given, *n_unmatched = 0 if given.
+ * KSH_INVALID_ARGUMENT, each with a message that names the field.  Before the index is dereferenced: NULL seqs, idx,
+ * req or n_runs; struct_size smaller than the struct; what ksh_seq_hits refuses about sizes, route and
+ * pass_positions; what ksh_kss_select_class_ids refuses about rows and n_classes (NULL, out of range, not strictly
+ * ascending, with the first offending index); n_cols outside [1, 128] with non-NULL cols; a negative capacity; a NULL
+ * d_run_start or d_run_class with capacity > 0.  After reading only the index's host fields: an id outside
+ * [0, n_nodes); a repeated id; NULL cols on an index of more than 128 nodes; a row with a bit at or above n_cols;
+ * K < 4.  On the device, before the words are read: lens[s] == UINT32_MAX, sum(lens + K) != n_bases.  The index still
+ * serves after any refusal.
+ * pass_positions: as in ksh_seq_hits, with 12 + 8 W bytes of scratch per position (the k-mer, the class, the row); the
+ * default keeps that within 256 MiB and a pass within the join's 2^24 queries.  The result does not depend on it.
+ * The call is stateless like its siblings: scratch comes from the context's pool (that of a pass, 8 bytes per
+ * sequence, 16 bytes per class and 32 bytes per slot of a table of the next power of two >= 2 * n_classes slots) and
+ * is given back before the call returns; it keeps no plan, joins no plan group and ends no pending plan.  It
+ * synchronises the index's context stream once for the size check, once per pass on the join route, and once at the
+ * end.  ksh_kss_index_routes reports SEARCH / JOIN / OVERSIZE / CHUNKED / SEQ_PASSES as for ksh_seq_hits.  As there,
+ * the sequences come first and the index second.  The index must be usable as for ksh_kss_index_query.
+ * Timing kinds (ksh_ctx_enable_timing): 6 = the extraction and look-up of a pass, 7 = its classification and runs. */
+int ksh_seq_class_runs(const ksh_spss_view* seqs, ksh_kss_index* idx, const ksh_seq_paint* req,
+                       int64_t capacity, int64_t* d_run_offsets, uint32_t* d_run_start, uint32_t* d_run_class,
+                       int64_t* n_runs, int64_t* n_unmatched);
 
 #ifdef __cplusplus
 }

@@ -431,6 +431,65 @@ class KmerSetSetIndex {
     return {Set::FromDevice(std::move(off), std::move(keys), n), std::move(out)};
   }
 
+  // Sequences painted with colour classes (ksh_seq_class_runs): the runs of string s are runs offsets[s] ..
+  // offsets[s + 1); run r begins at k-mer position start[r] of its string (the first run of a string at 0), ends
+  // before the next run of the string begins or with the string, and every k-mer position of it has the membership
+  // pattern classes[cls[r]] over cols -- or, with cls[r] == kNoClass, a pattern that `classes` does not hold.
+  // n_unmatched is the number of such positions.
+  struct ClassRuns {
+    std::vector<std::int64_t> offsets;
+    std::vector<std::uint32_t> start, cls;
+    std::int64_t n_unmatched = 0;
+  };
+  static constexpr std::uint32_t kNoClass = KSH_CLASS_NONE;
+  // `classes`: what ColorClasses(cols) returned, or any part of it in the same order.  A k-mer that no node holds,
+  // or only nodes outside cols, has the zero pattern.  allow_unmatched = false: a position whose pattern `classes`
+  // does not hold is refused.  capacity: the runs there is room for; 0: one call counts them and a second one
+  // writes them; a given capacity that is too small is refused with the number of runs in the message.
+  ClassRuns Paint(const KmerSetCompact<K, N, KeyType>& sequences, const std::vector<int>& cols,
+                  const std::vector<ColorClass>& classes, bool canonical = true, bool allow_unmatched = true,
+                  std::int64_t capacity = 0) const {
+    const std::vector<std::int32_t> ids(cols.begin(), cols.end());
+    std::vector<std::uint64_t> rows;
+    rows.reserve(2 * classes.size());
+    for (const ColorClass& c : classes) rows.insert(rows.end(), {c.row[0], c.row[1]});
+    ksh_seq_paint req{};
+    req.struct_size = sizeof(req);
+    req.cols = ids.empty() ? nullptr : ids.data();
+    req.n_cols = static_cast<std::int32_t>(ids.size());
+    req.canonicalize = canonical ? 1 : 0;
+    req.rows = rows.data();
+    req.n_classes = static_cast<std::int64_t>(classes.size());
+    const ksh_spss_view v = sequences.View();
+    const std::size_t n = std::size_t(sequences.StringCount());
+    ClassRuns out;
+    std::int64_t n_runs = 0;
+    std::int64_t* missing = allow_unmatched ? &out.n_unmatched : nullptr;
+    ksc::DeviceBuffer off((n + 1) * 8);
+    if (capacity <= 0) {
+      ksc::Check(ksh_seq_class_runs(&v, index_, &req, 0, nullptr, nullptr, nullptr, &n_runs, missing));
+      capacity = n_runs;
+    }
+    const std::size_t room = std::max<std::size_t>(std::size_t(capacity) * 4, 16);
+    ksc::DeviceBuffer start(room), cls(room);
+    ksc::Check(ksh_seq_class_runs(&v, index_, &req, capacity, static_cast<std::int64_t*>(off.get()),
+                                  capacity > 0 ? static_cast<std::uint32_t*>(start.get()) : nullptr,
+                                  capacity > 0 ? static_cast<std::uint32_t*>(cls.get()) : nullptr, &n_runs, missing));
+    out.offsets = off.ToHost<std::int64_t>(n + 1);
+    if (n_runs > 0) {
+      out.start = start.ToHost<std::uint32_t>(std::size_t(n_runs));
+      out.cls = cls.ToHost<std::uint32_t>(std::size_t(n_runs));
+    }
+    return out;
+  }
+  // The same for strings over ACGT, each at least K long.
+  ClassRuns Paint(const std::vector<std::string>& sequences, const std::vector<int>& cols,
+                  const std::vector<ColorClass>& classes, bool canonical = true, bool allow_unmatched = true,
+                  std::int64_t capacity = 0) const {
+    return Paint(KmerSetCompact<K, N, KeyType>::FromStrings(sequences), cols, classes, canonical, allow_unmatched,
+                 capacity);
+  }
+
  private:
   static ksh_kss_selection Selection(const std::vector<std::int32_t>& ids, int min_count, int max_count,
                                      const std::vector<std::int32_t>& req, const std::vector<std::int32_t>& exc) {

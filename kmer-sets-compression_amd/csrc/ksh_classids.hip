@@ -22,7 +22,6 @@ using namespace ksh::pc;
 namespace {
 
 constexpr uint32_t kClassNone = KSH_CLASS_NONE;
-constexpr int64_t kMaxClasses = int64_t(1) << 24;
 // device results of a call: [0] selected k-mers whose row the table does not hold, [1] buckets that missed their
 // offsets, [2] rows that found no slot when the table was built (cannot happen: at most half load)
 constexpr int kAccWords = 4;
@@ -39,7 +38,8 @@ static_assert(classids_lds_bytes(kMaxNodes) == 51280 && classids_lds_bytes(kMaxN
 namespace ksh {
 
 // Row c of rows[0 .. n) into the table with the word c + 1.  The rows are distinct (the host has checked that they
-// ascend strictly), so each is inserted once and its slot's fourth word ends as c + 1.
+// ascend strictly), so each is inserted once and its slot's fourth word ends as c + 1.  *acc counts the rows that
+// found no slot.
 __global__ __launch_bounds__(256) void k_class_table(const uint64_t* __restrict__ rows, int64_t n,
                                                      unsigned long long* __restrict__ g_tab, uint32_t g_mask,
                                                      unsigned long long* __restrict__ acc) {
@@ -47,7 +47,52 @@ __global__ __launch_bounds__(256) void k_class_table(const uint64_t* __restrict_
   if (c >= n) return;
   int claims = 0;
   if (!cls_insert<4, 1>(g_tab, g_mask, rows[2 * c], rows[2 * c + 1], static_cast<unsigned long long>(c) + 1, &claims))
-    atomicAdd(&acc[2], 1ull);
+    atomicAdd(acc, 1ull);
+}
+
+int class_table_check_size(const uint64_t* rows, int64_t n_classes) {
+  if (!rows) return fail(KSH_INVALID_ARGUMENT, "rows is NULL");
+  if (n_classes < 1 || n_classes > kMaxClasses)
+    return fail(KSH_INVALID_ARGUMENT, "n_classes = %lld is outside [1, %lld]", (long long)n_classes,
+                (long long)kMaxClasses);
+  return KSH_OK;
+}
+
+int class_table_check_order(const uint64_t* rows, int64_t n_classes) {
+  for (int64_t c = 1; c < n_classes; c++) {
+    const uint64_t a0 = rows[2 * c - 2], a1 = rows[2 * c - 1], b0 = rows[2 * c], b1 = rows[2 * c + 1];
+    if (!(b1 > a1 || (b1 == a1 && b0 > a0)))
+      return fail(KSH_INVALID_ARGUMENT, "rows[%lld] is not above rows[%lld]: rows must be strictly ascending by "
+                                        "(rows[2 c + 1], rows[2 c]), as ksh_kss_color_classes returns them",
+                  (long long)c, (long long)(c - 1));
+  }
+  return KSH_OK;
+}
+
+int class_table_check_cols(const uint64_t* rows, int64_t n_classes, int n_cols) {
+  const uint64_t beyond[2] = {n_cols >= 64 ? 0 : ~uint64_t(0) << n_cols,
+                              n_cols >= 128 ? 0 : n_cols <= 64 ? ~uint64_t(0) : ~uint64_t(0) << (n_cols - 64)};
+  for (int64_t c = 0; c < n_classes; c++)
+    if ((rows[2 * c] & beyond[0]) | (rows[2 * c + 1] & beyond[1]))
+      return fail(KSH_INVALID_ARGUMENT, "rows[%lld] has a bit at or above n_cols = %d: the table is that of other "
+                                        "columns", (long long)c, n_cols);
+  return KSH_OK;
+}
+
+int class_table_build(ksh_ctx* ctx, const uint64_t* rows, int64_t n_classes, PoolBuf* tab, PoolBuf* up,
+                      unsigned long long* d_noslot, int64_t* slots_out) {
+  int64_t slots = 2;
+  while (slots < 2 * n_classes) slots <<= 1;
+  KSH_TRY(pool_alloc(ctx, size_t(slots) * 32, &tab->p));
+  KSH_TRY(pool_alloc(ctx, size_t(n_classes) * 16, &up->p));
+  auto* g_tab = static_cast<unsigned long long*>(tab->p);
+  KSH_HIP(hipMemsetAsync(g_tab, 0, size_t(slots) * 32, ctx->stream));
+  KSH_HIP(hipMemcpyAsync(up->p, rows, size_t(n_classes) * 16, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_class_table, dim3(unsigned((n_classes + 255) / 256)), dim3(256), 0, ctx->stream,
+                     static_cast<const uint64_t*>(up->p), n_classes, g_tab, uint32_t(slots - 1), d_noslot);
+  KSH_HIP(hipGetLastError());
+  *slots_out = slots;
+  return KSH_OK;
 }
 
 // The consumer of the walk that writes keys and class ids: SelectConsumer<KeyT, true> with an id beside every key.
@@ -193,46 +238,25 @@ extern "C" int ksh_kss_select_class_ids(const ksh_kss_selection* sel, ksh_kss_in
   KSH_TRY(check_request(sel, idx));
   if (!d_offsets) return fail(KSH_INVALID_ARGUMENT, "d_offsets is NULL");
   if (n_keys < 0) return fail(KSH_INVALID_ARGUMENT, "n_keys = %lld is negative", (long long)n_keys);
-  if (!rows) return fail(KSH_INVALID_ARGUMENT, "rows is NULL");
-  if (n_classes < 1 || n_classes > kMaxClasses)
-    return fail(KSH_INVALID_ARGUMENT, "n_classes = %lld is outside [1, %lld]", (long long)n_classes,
-                (long long)kMaxClasses);
+  KSH_TRY(class_table_check_size(rows, n_classes));
   if (n_keys > 0 && !d_class_ids)
     return fail(KSH_INVALID_ARGUMENT, "d_class_ids is NULL with n_keys = %lld", (long long)n_keys);
-  for (int64_t c = 1; c < n_classes; c++) {
-    const uint64_t a0 = rows[2 * c - 2], a1 = rows[2 * c - 1], b0 = rows[2 * c], b1 = rows[2 * c + 1];
-    if (!(b1 > a1 || (b1 == a1 && b0 > a0)))
-      return fail(KSH_INVALID_ARGUMENT, "rows[%lld] is not above rows[%lld]: rows must be strictly ascending by "
-                                        "(rows[2 c + 1], rows[2 c]), as ksh_kss_color_classes returns them",
-                  (long long)c, (long long)(c - 1));
-  }
+  KSH_TRY(class_table_check_order(rows, n_classes));
   const IndexShape x = index_shape(idx);
   ColList list{};
   SelParams p{};
   int n_cols = 0;
   KSH_TRY(resolve_request(sel, x, &list, &n_cols, &p));
-  const uint64_t beyond[2] = {n_cols >= 64 ? 0 : ~uint64_t(0) << n_cols,
-                              n_cols >= 128 ? 0 : n_cols <= 64 ? ~uint64_t(0) : ~uint64_t(0) << (n_cols - 64)};
-  for (int64_t c = 0; c < n_classes; c++)
-    if ((rows[2 * c] & beyond[0]) | (rows[2 * c + 1] & beyond[1]))
-      return fail(KSH_INVALID_ARGUMENT, "rows[%lld] has a bit at or above n_cols = %d: the table is that of other "
-                                        "columns", (long long)c, n_cols);
+  KSH_TRY(class_table_check_cols(rows, n_classes, n_cols));
   ksh_ctx* ctx = x.ctx;
   PoolBuf proj(ctx), acc(ctx), tab(ctx), up(ctx);
   KSH_TRY(walk_prologue(idx, x, list, n_cols, &proj));
-  int64_t slots = 2;
-  while (slots < 2 * n_classes) slots <<= 1;
   KSH_TRY(pool_alloc(ctx, size_t(kAccWords) * 8, &acc.p));
-  KSH_TRY(pool_alloc(ctx, size_t(slots) * 32, &tab.p));
-  KSH_TRY(pool_alloc(ctx, size_t(n_classes) * 16, &up.p));
   auto* d_acc = static_cast<unsigned long long*>(acc.p);
-  auto* g_tab = static_cast<unsigned long long*>(tab.p);
   KSH_HIP(hipMemsetAsync(d_acc, 0, size_t(kAccWords) * 8, ctx->stream));
-  KSH_HIP(hipMemsetAsync(g_tab, 0, size_t(slots) * 32, ctx->stream));
-  KSH_HIP(hipMemcpyAsync(up.p, rows, size_t(n_classes) * 16, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_class_table, dim3(unsigned((n_classes + 255) / 256)), dim3(256), 0, ctx->stream,
-                     static_cast<const uint64_t*>(up.p), n_classes, g_tab, uint32_t(slots - 1), d_acc);
-  KSH_HIP(hipGetLastError());
+  int64_t slots = 0;
+  KSH_TRY(class_table_build(ctx, rows, n_classes, &tab, &up, d_acc + 2, &slots));
+  auto* g_tab = static_cast<unsigned long long*>(tab.p);
   KSH_TRY(KSH_BY_KEY(x.g.key_bytes, launch_class_ids, ctx, x, static_cast<const uint64_t*>(proj.p), p, d_offsets,
                      d_keys, d_class_ids, n_keys, g_tab, slots, d_acc));
   KSH_HIP(hipMemcpyAsync(ctx->h_pinned, d_acc, size_t(kAccWords) * 8, hipMemcpyDeviceToHost, ctx->stream));

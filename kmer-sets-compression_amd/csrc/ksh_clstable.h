@@ -75,6 +75,21 @@ __device__ __forceinline__ unsigned long long cls_peek(const unsigned long long*
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The class table of a caller (ksh_kss_select_class_ids, ksh_seq_class_runs): rows as ksh_kss_color_classes returns
+// them, looked up on the device by cls_find<4, 1>, whose word is the row's position + 1.  ksh_classids.hip.
+constexpr int64_t kMaxClasses = int64_t(1) << 24;
+// Host checks that need no index: rows not NULL and n_classes in [1, kMaxClasses]; the rows strictly ascending by
+// (rows[2 c + 1], rows[2 c]), with the first offending index in the message.
+int class_table_check_size(const uint64_t* rows, int64_t n_classes);
+int class_table_check_order(const uint64_t* rows, int64_t n_classes);
+// ... and one that needs the number of columns: no row has a bit at or above n_cols.
+int class_table_check_cols(const uint64_t* rows, int64_t n_classes, int n_cols);
+// Uploads the rows (up: 16 bytes per class) and inserts row c with the word c + 1 into a zeroed table of *slots =
+// the next power of two >= 2 * n_classes slots of 32 bytes (tab), all from the context's pool and on its stream.
+// *d_noslot (device, zeroed by the caller) counts the rows that found no slot (cannot happen: at most half load).
+int class_table_build(ksh_ctx* ctx, const uint64_t* rows, int64_t n_classes, pc::PoolBuf* tab, pc::PoolBuf* up,
+                      unsigned long long* d_noslot, int64_t* slots);
+
 }  // namespace ksh
 
 #endif

@@ -649,11 +649,11 @@ int launch_xor_keys(ksh_ctx* ctx, const ksh_set_view* s, unsigned blocks, unsign
 
 extern "C" {
 
-int ksh_version(void) { return 10; }  // 2: ksh_comm_fns::struct_size, lanes, encode routes; 3: ksh_spss_cover_*;
+int ksh_version(void) { return 11; }  // 2: ksh_comm_fns::struct_size, lanes, encode routes; 3: ksh_spss_cover_*;
                                      // 4: ksh_kss_index_*; 5: ksh_*_write_for (the encode, cover, text and FASTA
                                      // writes that name their plan); 6: ksh_seq_hits;
                                      // 7: ksh_kss_pair_counts; 8: ksh_kss_select_count, ksh_kss_select_keys;
-                                     // 9: ksh_kss_color_classes; 10: ksh_kss_select_class_ids
+                                     // 9: ksh_kss_color_classes; 10: ksh_kss_select_class_ids; 11: ksh_seq_class_runs
 
 const char* ksh_last_error(void) { return g_last_error.c_str(); }
 

@@ -9,8 +9,8 @@
 //   3. sums the rows' columns per sequence (k_seq_count: a wave per run of positions, ballots and popcounts)
 //      into d_hits, one atomicAdd per (run of one sequence, node) with a non-zero count.
 // Patterns and rows live in the context's pool, not in its arena: the join resets the arena.
-#include "ksh_internal.h"
 #include "ksh_kmer.h"
+#include "ksh_seq.h"
 
 #include <algorithm>
 
@@ -20,14 +20,10 @@ constexpr int kRun = 16;              // extraction: consecutive positions per t
 constexpr int kExtractThreads = 256;
 constexpr int kCountChunk = 512;      // counting: consecutive positions per wave
 constexpr int kCountThreads = 256;
-constexpr int64_t kPassBytes = int64_t(256) << 20;  // default pass: patterns + rows fit this
-constexpr int64_t kMaxPass = int64_t(1) << 28;
 
 // The default pass: as many positions as keep the pass's patterns (8 bytes) and rows (8 W bytes) within
-// kPassBytes, at most the join's own pass of 2^24 queries: 2^24 positions at W = 1, about 1.9 * 10^6 at W = 16.
-int64_t default_pass(int words) {
-  return std::min<int64_t>(int64_t(1) << 24, (kPassBytes / (8 + 8 * words)) & ~int64_t(4095));
-}
+// kSeqPassBytes, at most the join's own pass of 2^24 queries: 2^24 positions at W = 1, about 1.9 * 10^6 at W = 16.
+int64_t default_pass(int words) { return ksh::seq_default_pass(8 + 8 * words); }
 
 struct PoolBuf {
   ksh_ctx* ctx;
@@ -43,15 +39,6 @@ struct PoolBuf {
 }  // namespace
 
 namespace ksh {
-
-// The last sequence of [lo, hi] whose first position is <= p.
-__device__ __forceinline__ int64_t seq_of(const int64_t* __restrict__ pstart, int64_t lo, int64_t hi, int64_t p) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (pstart[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // Positions per sequence, for the scan; bad[0] = the smallest s with lens[s] == UINT32_MAX (lens + 1 would wrap
 // in the type of the container).
@@ -189,13 +176,7 @@ static void launch_count(hipStream_t st, const uint64_t* rows, int words, const 
                      n_strings, p0, m, n_nodes, hits);
 }
 
-}  // namespace ksh
-
-using namespace ksh;
-
-extern "C" int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int canonicalize, int route,
-                            int64_t pass_positions, uint32_t* d_hits) {
-  if (!seqs || !idx || !d_hits) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
+int seq_check_request(const ksh_spss_view* seqs, int route, int64_t pass_positions) {
   if (seqs->n_strings < 0 || seqs->n_bases < 0)
     return fail(KSH_INVALID_ARGUMENT, "negative size: %lld strings, %lld bases", (long long)seqs->n_strings,
                 (long long)seqs->n_bases);
@@ -203,6 +184,50 @@ extern "C" int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int c
     return fail(KSH_INVALID_ARGUMENT, "pass_positions = %lld is negative", (long long)pass_positions);
   if (route < 0 || route > 2) return fail(KSH_INVALID_ARGUMENT, "route = %d (0 auto, 1 search, 2 join)", route);
   if (seqs->n_strings > 0 && (!seqs->d_words || !seqs->d_lens)) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
+  return KSH_OK;
+}
+
+int seq_positions(ksh_ctx* ctx, const ksh_spss_view* seqs, int k, int64_t* pstart, unsigned long long* bad,
+                  int64_t* total_out) {
+  const int64_t n = seqs->n_strings;
+  KSH_TRY(arena_reserve(ctx, size_t(n) / 32 + (size_t(1) << 20)));  // the scan's block sums
+  arena_reset(ctx);
+  KSH_HIP(hipMemsetAsync(bad, 0xFF, 8, ctx->stream));
+  hipLaunchKernelGGL(k_seq_sizes, dim3(unsigned((n + 255) / 256)), dim3(256), 0, ctx->stream, seqs->d_lens, n, pstart,
+                     bad);
+  KSH_HIP(hipGetLastError());
+  KSH_TRY(scan_exclusive_i64(ctx, pstart, pstart, n, pstart + n));
+  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, pstart + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+  KSH_HIP(hipMemcpyAsync(ctx->h_pinned + 1, bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+  KSH_HIP(hipStreamSynchronize(ctx->stream));
+  const int64_t total = ctx->h_pinned[0];
+  if (ctx->h_pinned[1] != -1)
+    return fail(KSH_INVALID_ARGUMENT, "lens[%lld] = UINT32_MAX: lens + 1 does not fit the container's type",
+                (long long)ctx->h_pinned[1]);
+  if (total + n * int64_t(k - 1) != seqs->n_bases)
+    return fail(KSH_INVALID_ARGUMENT, "sum(lens + K) = %lld but n_bases = %lld", (long long)(total + n * int64_t(k - 1)),
+                (long long)seqs->n_bases);
+  *total_out = total;
+  return KSH_OK;
+}
+
+int seq_extract(ksh_ctx* ctx, const ksh_spss_view* seqs, const int64_t* pstart, int64_t p0, int64_t m, int k,
+                int canon, uint64_t* pat) {
+  const int64_t per_block = int64_t(kExtractThreads) * kRun;
+  hipLaunchKernelGGL(k_seq_extract, dim3(unsigned((m + per_block - 1) / per_block)), dim3(kExtractThreads), 0,
+                     ctx->stream, seqs->d_words, pstart, seqs->n_strings, p0, m, k, canon, pat);
+  KSH_HIP(hipGetLastError());
+  return KSH_OK;
+}
+
+}  // namespace ksh
+
+using namespace ksh;
+
+extern "C" int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int canonicalize, int route,
+                            int64_t pass_positions, uint32_t* d_hits) {
+  if (!seqs || !idx || !d_hits) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
+  KSH_TRY(seq_check_request(seqs, route, pass_positions));
   const IndexShape x = index_shape(idx);
   const int k = x.g.k;
   if (k < 4) return fail(KSH_INVALID_ARGUMENT, "k = %d: sequence queries need K >= 4", k);
@@ -222,26 +247,11 @@ extern "C" int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int c
   KSH_TRY(pool_alloc(ctx, 16, &bad_buf.p));
   auto* pstart = static_cast<int64_t*>(pstart_buf.p);
   auto* bad = static_cast<unsigned long long*>(bad_buf.p);
-  KSH_TRY(arena_reserve(ctx, size_t(n) / 32 + (size_t(1) << 20)));  // the scan's block sums
-  arena_reset(ctx);
-  KSH_HIP(hipMemsetAsync(bad, 0xFF, 8, ctx->stream));
-  hipLaunchKernelGGL(k_seq_sizes, dim3(unsigned((n + 255) / 256)), dim3(256), 0, ctx->stream, seqs->d_lens, n, pstart,
-                     bad);
-  KSH_HIP(hipGetLastError());
-  KSH_TRY(scan_exclusive_i64(ctx, pstart, pstart, n, pstart + n));
-  KSH_HIP(hipMemcpyAsync(ctx->h_pinned, pstart + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-  KSH_HIP(hipMemcpyAsync(ctx->h_pinned + 1, bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-  KSH_HIP(hipStreamSynchronize(ctx->stream));
-  const int64_t total = ctx->h_pinned[0];  // k-mer positions in all
-  if (ctx->h_pinned[1] != -1)
-    return fail(KSH_INVALID_ARGUMENT, "lens[%lld] = UINT32_MAX: lens + 1 does not fit the container's type",
-                (long long)ctx->h_pinned[1]);
-  if (total + n * int64_t(k - 1) != seqs->n_bases)
-    return fail(KSH_INVALID_ARGUMENT, "sum(lens + K) = %lld but n_bases = %lld", (long long)(total + n * int64_t(k - 1)),
-                (long long)seqs->n_bases);
+  int64_t total = 0;  // k-mer positions in all
+  KSH_TRY(seq_positions(ctx, seqs, k, pstart, bad, &total));
 
   // 2. the passes
-  const int64_t pass = std::min(pass_positions > 0 ? pass_positions : default_pass(x.words), kMaxPass);
+  const int64_t pass = std::min(pass_positions > 0 ? pass_positions : default_pass(x.words), kSeqMaxPass);
   const int64_t cap = std::min(pass, total);
   KSH_TRY(pool_alloc(ctx, size_t(cap) * 8, &pat_buf.p));
   KSH_TRY(pool_alloc(ctx, size_t(cap) * size_t(x.words) * 8, &rows_buf.p));
@@ -253,10 +263,7 @@ extern "C" int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int c
   index_set_routes(idx, 0);
   for (int64_t p0 = 0; p0 < total; p0 += pass) {
     const int64_t m = std::min(pass, total - p0);
-    const int64_t per_block = int64_t(kExtractThreads) * kRun;
-    hipLaunchKernelGGL(k_seq_extract, dim3(unsigned((m + per_block - 1) / per_block)), dim3(kExtractThreads), 0,
-                       ctx->stream, seqs->d_words, pstart, n, p0, m, k, canonicalize ? 1 : 0, pat);
-    KSH_HIP(hipGetLastError());
+    KSH_TRY(seq_extract(ctx, seqs, pstart, p0, m, k, canonicalize ? 1 : 0, pat));
     const bool join = route == 2 || (route == 0 && index_auto_joins(idx, m));
     routes |= join ? KSH_QROUTE_JOIN : KSH_QROUTE_SEARCH;
     KSH_TRY(index_lookup(idx, join, pat, m, 0, rows));  // (the patterns are canonical already, if asked)

@@ -66,6 +66,13 @@ class Selection(C.Structure):
                 ("n_require", C.c_int32), ("exclude", C.POINTER(C.c_int32)), ("n_exclude", C.c_int32)]
 
 
+class SeqPaint(C.Structure):
+    """ksh_seq_paint; cols and rows are host arrays."""
+    _fields_ = [("struct_size", C.c_size_t), ("cols", C.POINTER(C.c_int32)), ("n_cols", C.c_int32),
+                ("canonicalize", C.c_int32), ("rows", C.POINTER(C.c_uint64)), ("n_classes", C.c_int64),
+                ("route", C.c_int32), ("pass_positions", C.c_int64)]
+
+
 def build(force=False):
     """Compiles the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC_DIR, f) for f in os.listdir(CSRC_DIR) if f.endswith((".hip", ".h"))]
@@ -199,6 +206,8 @@ def lib():
                                                C.POINTER(i64)]),
         "ksh_kss_color_classes": (C.c_int, [C.POINTER(i32), i32, vp, i64, C.POINTER(C.c_uint64), C.POINTER(i64),
                                             C.POINTER(i64)]),
+        "ksh_seq_class_runs": (C.c_int, [C.POINTER(SpssView), vp, C.POINTER(SeqPaint), i64, vp, vp, vp, C.POINTER(i64),
+                                         C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1279,6 +1288,74 @@ class KssIndex:
         self.select_class_ids(off, n, rows, keys, ids, cols, min_count, max_count, require, exclude,
                               allow_unmatched=allow_unmatched)
         return DeviceSet(self.g, off, keys, n), ids[:n], rows, counts
+
+    def class_runs_raw(self, seqs, rows, capacity, offsets=None, start=None, cls=None, cols=None, canonicalize=True,
+                       route=0, pass_positions=0, allow_unmatched=True):
+        """ksh_seq_class_runs, one call: (rc, n_runs, n_unmatched or None).  seqs: a DeviceSpss; offsets, start, cls:
+        device tensors or None.  rc is KSH_OK or KSH_FAILED_PRECONDITION (too small a capacity, or a row the table
+        does not hold without allow_unmatched: the message is ksh_last_error); anything else is raised."""
+        import torch
+
+        with torch.cuda.stream(self.ctx.stream):
+            h = self._handle()
+            keep = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+            ids = None if cols is None else (keep if keep.size else np.zeros(1, dtype=np.int32)).ctypes.data_as(
+                C.POINTER(C.c_int32))  # (never NULL)
+            table = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+            req = SeqPaint(C.sizeof(SeqPaint), ids, 0 if cols is None else int(keep.size), int(bool(canonicalize)),
+                           None if table is None else table.ctypes.data_as(C.POINTER(C.c_uint64)),
+                           0 if table is None else table.size // 2, int(route), int(pass_positions))
+            view = seqs.view()
+            n_runs, missing = C.c_int64(-1), C.c_int64()
+            rc = lib().ksh_seq_class_runs(C.byref(view), h, C.byref(req), int(capacity),
+                                          offsets.data_ptr() if offsets is not None else None,
+                                          start.data_ptr() if start is not None else None,
+                                          cls.data_ptr() if cls is not None else None, C.byref(n_runs),
+                                          C.byref(missing) if allow_unmatched else None)
+            del keep, table
+            if rc not in (KSH_OK, KSH_FAILED_PRECONDITION):
+                check(rc)
+            return rc, n_runs.value, (missing.value if allow_unmatched else None)
+
+    def class_runs(self, seqs, rows, cols=None, canonicalize=True, route=0, pass_positions=0, capacity=None,
+                   allow_unmatched=True):
+        """ksh_seq_class_runs: the sequences of `seqs` (a DeviceSpss, or a list of str over ACGT, each at least K long)
+        cut into runs of consecutive k-mer positions of one colour class.  rows: a class table np.uint64[n, 2] as
+        color_classes(cols) returns it, or an ascending subset of it.  Returns (run_offsets, run_start, run_class,
+        n_unmatched): device tensors int64[n_seqs + 1], int32[n_runs], int32[n_runs] -- the runs of sequence s are
+        run_offsets[s] .. run_offsets[s + 1), run r begins at position run_start[r] of its sequence and has class
+        run_class[r], -1 (CLASS_NONE) where the table does not hold the position's row -- and the number of such
+        positions (None, and a refusal if there are any, with allow_unmatched=False).  capacity None: one call counts
+        the runs and a second one writes them; a given capacity is tried once."""
+        import torch
+
+        if not isinstance(seqs, DeviceSpss):
+            seqs = DeviceSpss.from_strings(self.g, list(seqs), self.ctx.device)
+        kw = dict(cols=cols, canonicalize=canonicalize, route=route, pass_positions=pass_positions,
+                  allow_unmatched=allow_unmatched)
+        with torch.cuda.stream(self.ctx.stream):
+            off = torch.zeros(seqs.n_strings + 1, dtype=torch.int64, device=self.ctx.device)
+        if capacity is None:
+            rc, capacity, _ = self.class_runs_raw(seqs, rows, 0, off, **kw)
+            check(rc)
+        capacity = int(capacity)
+        with torch.cuda.stream(self.ctx.stream):
+            start = torch.empty(max(capacity, 1), dtype=torch.int32, device=self.ctx.device)
+            cls = torch.empty(max(capacity, 1), dtype=torch.int32, device=self.ctx.device)
+        rc, n_runs, missing = self.class_runs_raw(seqs, rows, capacity, off, start if capacity else None,
+                                                  cls if capacity else None, **kw)
+        check(rc)
+        n_runs = min(n_runs, capacity)  # (capacity 0 only counts: the offsets are whole, the runs are not asked for)
+        return off, start[:n_runs], cls[:n_runs], missing
+
+    def paint(self, seqs, cols=None, canonicalize=True, route=0, pass_positions=0, allow_unmatched=True):
+        """class_runs with the whole table of the columns: (run_offsets, run_start, run_class, n_unmatched, rows,
+        counts), rows and counts being color_classes(cols).  A k-mer that no node of the index holds has the zero
+        row, which the table only holds if some k-mer of the structure lies outside every column: such positions are
+        -1 in run_class and counted in n_unmatched."""
+        rows, counts = self.color_classes(cols)
+        out = self.class_runs(seqs, rows, cols, canonicalize, route, pass_positions, None, allow_unmatched)
+        return out + (rows, counts)
 
     @staticmethod
     def class_matrix(rows, n_cols):
