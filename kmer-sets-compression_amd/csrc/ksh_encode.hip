@@ -33,7 +33,8 @@
 //   k_ruler_walk / k_ruler_heads / k_choose / k_loops / k_emit   the same with a record per k-mer:
 //                 sets with a non-branching loop (spelled from its smallest k-mer, spss.h:585-610)
 //   k_head_counts / scans / k_unitig_fill   unitig ids in the reference's push order
-//   k_edges       <= 4 edges per unitig side, in the reference's enumeration order
+//   k_edges       <= 4 edges per unitig side, in the reference's enumeration order; a side that never had a
+//                 neighbour (link `none`, no mark of k_link_cut's) has none and is not searched for
 //   k_match_*     lexicographically-first maximal matching by rounds of mutual minima
 //                 == the sequential greedy sweep of spss.h:1445-1499
 //   k_dsu_* / k_loop_cut    loops of the path cover: components by parallel union-find, a loop cut
@@ -51,6 +52,10 @@
 #include <cstddef>
 #include <cstdlib>
 #include <string>
+#ifdef KSH_EDGES_DEBUG  // (make BUILD=build_edges OUT=libkmersets_hip_edges.so EXTRA=-DKSH_EDGES_DEBUG: k_edges' branch counts on stderr)
+#include <cstdio>
+#include <vector>
+#endif
 
 namespace ksh {
 
@@ -235,21 +240,59 @@ __global__ __launch_bounds__(256) void k_adjacency(DevSet<KeyT> set, uint32_t* _
 // ever change to kNone, and a
 // k-mer decides from its own two entries alone whether it cuts (`several` is never overwritten
 // by another k-mer), so the order of the threads does not matter.
+// cut_marks (a bit per side, zeroed; null: none kept) remembers the sides that had a neighbour and lost the
+// link here: afterwards `none` and unmarked means the side never had a neighbour, which is all k_edges needs
+// to know of most unitig ends.  Every write of kNone sets the bit: a `several` side by its own k-mer, a
+// facing single by whoever clears it (a facing entry found `none` or `several` is marked by the one that
+// cleared it, or by its own k-mer).
+__device__ __forceinline__ void mark_cut(uint32_t* cut_marks, int64_t entry) {
+  if (cut_marks) atomicOr(cut_marks + (entry >> 5), 1u << (entry & 31));
+}
+// The kernel is a stream over the table that almost never finds work: a thread looks at kCutItems k-mers, a pair
+// of them per 16-byte load, the loads of a wave contiguous (8 bytes per thread ran at 4.4 TB/s on 10^8 k-mers).
+constexpr int kCutItems = 4;
+constexpr int kCutSpan = 256 * kCutItems;  // k-mers per workgroup
 template <typename KeyT, bool kDirected>
-__global__ __launch_bounds__(256) void k_link_cut(DevSet<KeyT> set, uint32_t* __restrict__ nbr) {
-  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= set.n) return;
-  const uint2 mine = reinterpret_cast<const uint2*>(nbr)[t];
-  if (mine.x != kMulti && mine.y != kMulti) return;
-  const uint64_t x = set.kmer(t);
-  const uint64_t rx = kDirected ? 0 : revcomp(x, set.k);
-  for (int side = 0; side < 2; side++) {
-    if ((side ? mine.y : mine.x) != kMulti) continue;
-    for_side_neighbours<KeyT, kDirected>(set, x, rx, t, side, [&](int64_t idx, uint32_t same) {
-      uint32_t* facing = nbr + 2 * idx + (same ? side : side ^ 1);
-      if (*reinterpret_cast<volatile uint32_t*>(facing) < kMulti) *reinterpret_cast<volatile uint32_t*>(facing) = kNone;
-    });
-    nbr[2 * t + side] = kNone;
+__global__ __launch_bounds__(256) void k_link_cut(DevSet<KeyT> set, uint32_t* __restrict__ nbr,
+                                                   uint32_t* __restrict__ cut_marks) {
+  static_assert(kCutItems % 2 == 0, "a pair of k-mers per load");
+  const int64_t t0 = int64_t(blockIdx.x) * kCutSpan + 2 * threadIdx.x;  // + 512 j: the thread's j-th pair
+  uint4 mine[kCutItems / 2];
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < kCutItems / 2; j++) {
+    const int64_t t = t0 + 512 * j;
+    if (t + 1 < set.n) {
+      mine[j] = *reinterpret_cast<const uint4*>(nbr + 2 * t);
+    } else if (t < set.n) {
+      const uint2 last = *reinterpret_cast<const uint2*>(nbr + 2 * t);
+      mine[j] = make_uint4(last.x, last.y, kNone, kNone);
+    } else {
+      mine[j] = make_uint4(kNone, kNone, kNone, kNone);
+    }
+    any |= mine[j].x == kMulti || mine[j].y == kMulti || mine[j].z == kMulti || mine[j].w == kMulti;
+  }
+  if (!any) return;
+#pragma unroll
+  for (int i = 0; i < kCutItems; i++) {
+    const uint32_t mine_l = (i & 1) ? mine[i / 2].z : mine[i / 2].x, mine_r = (i & 1) ? mine[i / 2].w : mine[i / 2].y;
+    if (mine_l != kMulti && mine_r != kMulti) continue;
+    const int64_t t = t0 + 512 * (i / 2) + (i & 1);
+    const uint64_t x = set.kmer(t);
+    const uint64_t rx = kDirected ? 0 : revcomp(x, set.k);
+    for (int side = 0; side < 2; side++) {
+      if ((side ? mine_r : mine_l) != kMulti) continue;
+      for_side_neighbours<KeyT, kDirected>(set, x, rx, t, side, [&](int64_t idx, uint32_t same) {
+        const int64_t entry = 2 * idx + (same ? side : side ^ 1);
+        uint32_t* facing = nbr + entry;
+        if (*reinterpret_cast<volatile uint32_t*>(facing) < kMulti) {
+          *reinterpret_cast<volatile uint32_t*>(facing) = kNone;
+          mark_cut(cut_marks, entry);
+        }
+      });
+      nbr[2 * t + side] = kNone;
+      mark_cut(cut_marks, 2 * t + side);
+    }
   }
 }
 
@@ -2665,12 +2708,26 @@ __global__ __launch_bounds__(256) void k_edges(DevSet<KeyT> set, int64_t n_verti
                                                 const uint32_t* __restrict__ u_last,
                                                 const uint32_t* __restrict__ head,
                                                 const uint32_t* __restrict__ uid,
+                                                const uint32_t* __restrict__ link,
+                                                const uint32_t* __restrict__ cut_marks,
                                                 uint32_t* __restrict__ edges, uint32_t* __restrict__ mate) {
   const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (v >= n_vertices) return;
   mate[v] = kNone;  // nobody is matched yet
   const uint32_t u = uint32_t(v >> 1), side = uint32_t(v & 1);
   const uint32_t st = side ? u_last[u] : u_first[u];
+  // Most unitig ends are dead ends: the side never had a neighbour, so there is no edge to look for.  The side
+  // of the k-mer behind this vertex is the one its state enters through (left end) or leaves through (right
+  // end); its entry of the link table is `none` either since the probe (no mark) or since k_link_cut took the
+  // link away (marked: neighbours, hence edges).  A live link at a unitig end -- a loop spelled from its
+  // smallest k-mer, a chain split at 2^30 steps -- has its neighbour too.  (cut_marks null: every side searches.)
+  if (cut_marks) {
+    const int64_t entry = 2 * int64_t(st >> 1) + ((st & 1) ^ side);
+    if (link[entry] == kNone && !((cut_marks[entry >> 5] >> (entry & 31)) & 1u)) {
+      *reinterpret_cast<uint4*>(edges + 4 * v) = make_uint4(kNone, kNone, kNone, kNone);
+      return;
+    }
+  }
   const int k = set.k;
   const uint64_t x = set.kmer(st >> 1);
   const uint64_t o = (st & 1) ? revcomp(x, k) : x;
@@ -3625,6 +3682,15 @@ inline bool emit_by_walking() {
   }();
   return on;
 }
+// KSH_EDGES=search: k_edges searches for the neighbours of every unitig side and k_link_cut keeps no marks (A/B
+// runs and tests); anything else: the sides that never had a neighbour store their four `none` at once.
+inline bool edges_skip_dead_ends() {
+  static const bool on = [] {
+    const char* e = getenv("KSH_EDGES");
+    return !(e && std::string(e) == "search");
+  }();
+  return on;
+}
 // KSH_L2_MIN: ruler records from which the pointer jumping runs in two levels (tests set it low).
 inline int64_t l2_threshold() {
   static const int64_t v = [] {
@@ -4084,10 +4150,19 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
       hipLaunchKernelGGL((k_adjacency<KeyT, false>), dim3(nblk(n)), dim3(256), 0, st, set, p->nbr, self_rc_flag);
     }
   }
+  // The cut marks, a bit per side, in the front of the link array: rc0 / rc1 are dead behind the probe's last
+  // kernel, the byte staging of encode_write_t comes after k_edges, and no kernel between them touches the array.
+  uint32_t* cut_marks = edges_skip_dead_ends() ? p->link : nullptr;
+  if (cut_marks) {
+    const size_t mark_bytes = size_t((2 * n + 31) / 32) * 4;
+    KSH_BOUND(mark_bytes <= p->link_bytes);
+    KSH_HIP(hipMemsetAsync(cut_marks, 0, mark_bytes, st));
+  }
+  const unsigned cut_blocks = unsigned((n + kCutSpan - 1) / kCutSpan);
   if (directed)
-    hipLaunchKernelGGL((k_link_cut<KeyT, true>), dim3(nblk(n)), dim3(256), 0, st, set, p->nbr);
+    hipLaunchKernelGGL((k_link_cut<KeyT, true>), dim3(cut_blocks), dim3(256), 0, st, set, p->nbr, cut_marks);
   else
-    hipLaunchKernelGGL((k_link_cut<KeyT, false>), dim3(nblk(n)), dim3(256), 0, st, set, p->nbr);
+    hipLaunchKernelGGL((k_link_cut<KeyT, false>), dim3(cut_blocks), dim3(256), 0, st, set, p->nbr, cut_marks);
   const uint32_t* link = p->nbr;  // the link table from here on
   const int64_t n_hblocks = (n + kHeadSpan - 1) / kHeadSpan;
   int64_t* b01 = p->c23;              // per-workgroup head counts (n / 2048 values each) live in
@@ -4277,7 +4352,31 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
                        p->u_sid, p->u_koff, p->u_flip, p->lens, p->str_start);
   } else {
     hipLaunchKernelGGL((k_edges<KeyT>), dim3(nblk(2 * n_u)), dim3(256), 0, st, set, 2 * n_u, directed,
-                       p->u_first, p->u_last, p->head, p->uid, p->edges, p->mate);
+                       p->u_first, p->u_last, p->head, p->uid, link, cut_marks, p->edges, p->mate);
+#ifdef KSH_EDGES_DEBUG
+    if (cut_marks) {
+      // how many unitig sides take which branch of k_edges, and the marked sides of the whole set (a few of
+      // them not unitig ends)
+      const size_t n_sides = size_t(2 * n), n_unitigs = size_t(n_u);
+      std::vector<uint32_t> h_link(n_sides), h_marks((n_sides + 31) / 32), h_first(n_unitigs), h_last(n_unitigs);
+      (void)hipStreamSynchronize(st);
+      (void)hipMemcpy(h_link.data(), link, h_link.size() * 4, hipMemcpyDeviceToHost);
+      (void)hipMemcpy(h_marks.data(), cut_marks, h_marks.size() * 4, hipMemcpyDeviceToHost);
+      (void)hipMemcpy(h_first.data(), p->u_first, h_first.size() * 4, hipMemcpyDeviceToHost);
+      (void)hipMemcpy(h_last.data(), p->u_last, h_last.size() * 4, hipMemcpyDeviceToHost);
+      long long marked = 0, dead = 0, cut = 0, live = 0;
+      for (uint32_t w : h_marks) marked += __builtin_popcount(w);
+      for (int64_t v = 0; v < 2 * n_u; v++) {
+        const uint32_t s = (v & 1) ? h_last[size_t(v >> 1)] : h_first[size_t(v >> 1)];
+        const size_t entry = 2 * size_t(s >> 1) + ((s & 1) ^ uint32_t(v & 1));
+        if (h_link[entry] != kNone) live++;
+        else if ((h_marks[entry >> 5] >> (entry & 31)) & 1u) cut++;
+        else dead++;
+      }
+      fprintf(stderr, "edges dbg: kmers %lld unitig-sides %lld dead-ends %lld cut-ends %lld live-ends %lld marked-sides %lld\n",
+              (long long)n, (long long)(2 * n_u), dead, cut, live, marked);
+    }
+#endif
     KSH_TRY(cover_stage(ctx, p, n_u, directed, mode == 2, g->k, &walk_rounds));
   }
   // string starts in bases (a scan over n_u slots: the slots past the last string hold zero)
