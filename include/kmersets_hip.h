@@ -270,7 +270,9 @@ int ksh_pair_weights(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sets, 
  * bases, 2 bits each (A=0 C=1 G=2 T=3), concatenated without separators in 64-bit
  * words -- base j of the stream at bits [63-2(j%32), 62-2(j%32)] of word j/32, i.e.
  * the reference's vector<bool> index 2j is the high bit (:236-251) -- plus
- * len - K per string (:222-223). */
+ * len - K per string (:222-223).  Nothing is promised about the bits of the last
+ * word behind base n_bases - 1: they may hold anything, and the decode and the k-mer count read no k-mer
+ * out of them. */
 typedef struct ksh_spss_view {
   const uint64_t* d_words; /* ceil(n_bases / 32) words            */
   const uint32_t* d_lens;  /* len - K per string                  */
