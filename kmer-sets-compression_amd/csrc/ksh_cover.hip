@@ -10,7 +10,8 @@
 //   k_cover_sizes  bases per string (lens + K), for the scan of the strings' base offsets
 //   k_cover_ends   first and last k-mer of every string; an open-addressing table of the ends, filled by
 //                  64-bit atomicCAS (a CAS that meets the same key from another string is a duplicate end);
-//                  the preconditions, each violation recorded with the smallest string index
+//                  the preconditions: a violation a string commits alone is recorded with the smallest such index,
+//                  a duplicate end with one of the strings that share the k-mer (whichever lost the CAS)
 //   k_cover_edges  <= 4 neighbours per side by looking up the candidates of the end (spss.h:1039-1206):
 //                  the edge table in exactly the layout k_edges writes
 //   k_cover_emit   every input base, reverse-complemented when its unitig is traversed flipped, to its place in
@@ -80,7 +81,9 @@ __global__ __launch_bounds__(256) void k_cover_sizes(const uint32_t* __restrict_
   if (i < n) sizes[i] = int64_t(lens[i]) + k;
 }
 
-// err[kCoverErr*]: the smallest string index that violates the precondition (~0: none).  The strings' base offsets
+// err[kCoverErr*]: a string index that violates the precondition (~0: none) -- the smallest one for the palindrome
+// and same-ends checks; for the duplicates the smallest among the strings whose insert met the key already there,
+// and which of the strings that share a k-mer gets there first is a race.  The strings' base offsets
 // must add up to the view's n_bases before anything is read (a view whose lens say otherwise reads nothing).
 __global__ __launch_bounds__(256) void k_cover_ends(const uint64_t* __restrict__ words, int64_t n_words,
                                                     const uint32_t* __restrict__ lens,

@@ -218,7 +218,10 @@ inline int64_t n_buckets(const ksh_geom* g) { return int64_t(1) << g->n_bucket_b
 inline int key_bits(const ksh_geom* g) { return 2 * g->k - g->n_bucket_bits; }
 
 // Kernels of ksh_spss_cover_* (ksh_cover.hip); the plan lives beside the encode's (ksh_encode.hip), whose
-// unitig-level stage it shares.  err[kCoverErr*] receives the smallest string index that violates a precondition.
+// unitig-level stage it shares.  err[kCoverErr*] receives a string index that violates the precondition: the
+// smallest one for the checks a string fails on its own (palindrome, same ends); for the three duplicate checks
+// one of the strings that share the repeated k-mer (the smallest among those that lost the table's atomicCAS --
+// which of them loses is a race).
 enum { kCoverErrBases = 0, kCoverErrPalindrome, kCoverErrSameEnds, kCoverErrDupEnd, kCoverErrDupFirst,
        kCoverErrDupLast, kCoverErrCount };
 void cover_launch_sizes(hipStream_t st, const uint32_t* lens, int64_t n, int k, int64_t* sizes);
