@@ -1,12 +1,13 @@
 """The cells, fabricated structures, requests and route models of the index geometry sweep, shared by
 test_index_reference_cpu.py (which checks on the CPU that every structure discriminates) and
-test_gpu_index_geometry.py (which runs the five index calls on them).  numpy only.
+test_gpu_index_geometry.py (which runs the seven index calls on them).  numpy only.
 
 A case is (cell, plain): the cell (k, N, key bytes) and whether the structure is the plain one (k-mers as written,
 canonical=False / canonicalize=False) or the canonical one."""
 import numpy as np
 
 import geometry_families as gf
+from index_reference import revcomp_string
 from kmersets import synth
 from test_gpu_geometry import CELLS, FAMILY_SEED, size_of
 
@@ -53,6 +54,11 @@ PERMUTED = [6, 5, 0, 3, 4]  # a permuted subset with the empty node and the inte
 SELECTS = [dict(cols=NONEMPTY, min_count=len(NONEMPTY)),
            dict(cols=[0, 1, 2], require=[0], max_count=1),
            dict(cols=PERMUTED, require=[0, 3], exclude=[4])]
+# The three class-id requests.  Each of SELECTS picks k-mers of a single class on every fabricated structure, so a
+# constant id array would pass on them; these pick several classes of which none holds more than half the selection
+# (test_index_reference_cpu.py asserts it per case): (a) the union over all seven nodes, the identity column list;
+# (b) the union over the permuted subset, whose rows project; (c) a proper subset, Get(0).
+CLASS_REQUESTS = [dict(cols=None), dict(cols=PERMUTED), dict(cols=None, require=[0])]
 
 # The pool without its smallest and largest k-mer (the sentinels, which every non-empty node gets) is dealt into seven
 # parts by the rank of each k-mer in a seeded permutation, rank % 16 -> part.  The first six ranks fill the parts the
@@ -157,3 +163,36 @@ def sequences_of(ref, plain, seed):
     random = synth.string_of_bases(synth.random_genome(3000, seed))
     repeat = kmer_strings(ref.kmers[ref.kmers.size // 2:][:1], k)[0] * 3
     return single + [random, repeat]
+
+
+PAINT_CUT = 400  # positions kept of each of the longest strings
+
+
+def cut_strings(whole_strings, k):
+    """The 6 longest strings and the 4 shortest of the others (ties by the text), each cut to at most PAINT_CUT
+    positions: a genome's pool makes a handful of strings of 10^4 positions and more, the shortest among them.
+    Where there are fewer than 6 strings, later windows of the longest one, a sixth of it apart, make up the 6."""
+    by_len = sorted(whole_strings, key=lambda s: (len(s), s))
+    longest = by_len[::-1][:6]
+    for j in range(1, 7 - len(longest)):
+        a = j * (len(longest[0]) - k + 1) // 6
+        longest.append(longest[0][a:])
+    return [s[:PAINT_CUT + k - 1] for s in longest + by_len[:-6][:4]]
+
+
+def paint_strings(whole_strings, ref, plain, seed):
+    """The strings a case paints: cut_strings of `whole_strings` -- the strings of node WHOLE as the test's own
+    encode made them: that node holds the whole pool, so its strings pass through k-mers of every part -- the
+    reverse complements of all ten, and sequences_of.  About 10^4 positions at the most."""
+    cut = cut_strings(whole_strings, ref.k)
+    return cut + [revcomp_string(s) for s in cut] + sequences_of(ref, plain, seed)
+
+
+def paint_strings_for_passes(whole_strings, ref, plain, seed):
+    """The strings painted in passes of 7 and of 257 positions: sequences_of with its random string cut to 400
+    positions, and the two longest cut strings at 250 positions each: at most 1000 positions and more than 257 (a
+    pass of 7 positions over more would be thousands of launches)."""
+    k = ref.k
+    few = sequences_of(ref, plain, seed)
+    few[-2] = few[-2][:400 + k - 1]
+    return few + [s[:250 + k - 1] for s in cut_strings(whole_strings, k)[:2]]

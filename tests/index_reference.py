@@ -1,5 +1,6 @@
-"""One numpy reference for the five calls that read a KssIndex (query, seq_hits, pair_counts, select / spectrum,
-color_classes), shared by test_index_reference_cpu.py and test_gpu_index_geometry.py.
+"""One numpy reference for the seven calls that read a KssIndex (query, seq_hits, pair_counts, select / spectrum,
+color_classes, select_class_ids and -- through tests/paint_reference.py, which takes an IndexReference -- class_runs),
+shared by test_index_reference_cpu.py and test_gpu_index_geometry.py.
 
 Everything derives from the membership matrix M of a structure: one row per distinct k-mer of all node sets, one
 column per node, M[q, i] = q in Get(i), where Get(i) is the union of the sets of the nodes reachable from i (i
@@ -54,6 +55,7 @@ class IndexReference:
         # M[q, i] = OR over the nodes j reachable from i of own[q, j]
         self.M = (own.astype(np.int64) @ reach.T.astype(np.int64)) > 0
         self.n_distinct = int(self.kmers.size)
+        self._classes = {}  # column list -> color_classes of it
 
     # ---- query -------------------------------------------------------------------------------------------------
     def query_rows(self, patterns, canonicalize):
@@ -127,13 +129,33 @@ class IndexReference:
 
     # ---- color_classes -----------------------------------------------------------------------------------------
     def color_classes(self, cols=None):
-        """(rows uint64[n, 2], counts int64[n]): np.unique of the packed 128-bit rows, ascending by (high, low)."""
-        rows = pack_rows(self.M[:, self.cols_of(cols)])
-        if rows.shape[0] == 0:
-            return np.zeros((0, 2), dtype=U), np.zeros(0, dtype=np.int64)
-        u, counts = np.unique(rows, axis=0, return_counts=True)
-        order = np.lexsort((u[:, 0], u[:, 1]))
-        return u[order], counts[order].astype(np.int64)
+        """(rows uint64[n, 2], counts int64[n]): np.unique of the packed 128-bit rows, ascending by (high, low).
+        Computed once per column list and shared: read-only arrays."""
+        key = tuple(self.cols_of(cols))
+        if key not in self._classes:
+            rows = pack_rows(self.M[:, list(key)])
+            if rows.shape[0] == 0:
+                u, counts = np.zeros((0, 2), dtype=U), np.zeros(0, dtype=np.int64)
+            else:
+                u, counts = np.unique(rows, axis=0, return_counts=True)
+                order = np.lexsort((u[:, 0], u[:, 1]))
+                u, counts = u[order], counts[order].astype(np.int64)
+            u.flags.writeable = counts.flags.writeable = False
+            self._classes[key] = (u, counts)
+        return self._classes[key]
+
+    # ---- select_class_ids --------------------------------------------------------------------------------------
+    def class_ids(self, rows, cols=None, min_count=1, max_count=None, require=(), exclude=()):
+        """(kmers, ids int64): the selected k-mers, ascending, as select() gives them, and for each the position in
+        `rows` of its row over cols (pack_rows(M[:, cols])), -1 where `rows` does not hold it.  rows: uint64[n, 2],
+        ascending by (high, low) -- color_classes(cols)[0] or an ascending subset of it."""
+        rows = np.ascontiguousarray(rows, dtype=U).reshape(-1, 2)
+        kmers = self.select(cols, min_count, max_count, require, exclude)
+        mine = pack_rows(self.M[np.searchsorted(self.kmers, kmers)][:, self.cols_of(cols)])
+        ids = np.full(kmers.size, -1, dtype=np.int64)
+        for c in range(rows.shape[0]):  # (a handful of rows; a row is in the table once, so no id is written twice)
+            ids[(mine[:, 0] == rows[c, 0]) & (mine[:, 1] == rows[c, 1])] = c
+        return kmers, ids
 
 
 def class_matrix(rows, n_cols):

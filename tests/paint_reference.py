@@ -10,6 +10,13 @@ from kmersets import synth
 NONE = -1  # KSH_CLASS_NONE as int32
 
 
+def with_zero_row(table):
+    """The table with the zero row, ascending by (high, low): every position then has a class."""
+    t = np.unique(np.concatenate([np.zeros((1, 2), dtype=np.uint64),
+                                  np.asarray(table, dtype=np.uint64).reshape(-1, 2)]), axis=0)
+    return t[np.lexsort((t[:, 0], t[:, 1]))]
+
+
 def position_ids(ref, strings, cols, table, canonicalize):
     """Per string the int64 class id of every k-mer position (NONE where the table does not hold the row)."""
     cols = ref.cols_of(cols)

@@ -9,6 +9,7 @@ import torch
 
 import oracle_lib as ol
 import paint_reference as pr
+from paint_reference import with_zero_row
 from index_reference import IndexReference, class_matrix, revcomp_string
 from kmersets import capi, synth
 
@@ -41,11 +42,6 @@ def build_both(ctx, k, n, kb, n_sets, size, seed):
 
 def kmer_strings(kmers, k):
     return ["".join("ACGT"[(int(x) >> (2 * (k - 1 - j))) & 3] for j in range(k)) for x in kmers]
-
-
-def with_zero_row(table):
-    t = np.unique(np.concatenate([np.zeros((1, 2), dtype=U), np.asarray(table, dtype=U).reshape(-1, 2)]), axis=0)
-    return t[np.lexsort((t[:, 0], t[:, 1]))]
 
 
 def host(result):

@@ -1,7 +1,8 @@
 """The numpy reference of the index geometry sweep (tests/index_reference.py) against brute force with Python sets on
 tiny structures, and the sweep's fabricated structures (tests/index_geometry_cells.py): every case must discriminate
 -- several colour classes of distinct sizes, k-mers of one column only and of all non-empty columns, a pair count
-that is no trivial value, selections that are neither empty nor everything -- so that a wrong answer on the GPU
+that is no trivial value, selections that are neither empty nor everything, class-id requests that select three
+classes or more of which none holds more than half of the selection -- so that a wrong answer on the GPU
 cannot hide in an empty or a total result.  The route models the GPU test asserts are computed and sanity-checked
 here too.  No GPU."""
 import collections
@@ -116,6 +117,20 @@ def test_reference_equals_brute_force(k, n_nodes, children, seed):
         assert rows[:, 1].tolist() == [0] * len(tally)
         assert list(zip(rows[:, 0].tolist(), counts.tolist())) == sorted(tally.items())
         assert np.array_equal(pack_rows(class_matrix(rows, len(ids))), rows)
+        # class ids: a dict from the row as an integer to its position in the table, asked per selected k-mer; the
+        # whole table, every second row of it and the rows above the first, with and without require / exclude
+        value = {q: sum((q in gets[c]) << a for a, c in enumerate(ids)) for q in every}
+        for r in requests + [dict(), dict(exclude=[ids[2]])]:
+            chosen = ref.select(cols, **r).tolist()
+            for table in (rows, rows[::2], rows[1:]):
+                at = {int(low): c for c, (low, high) in enumerate(table.tolist())}
+                kmers, got = ref.class_ids(table, cols, **r)
+                assert kmers.tolist() == chosen and got.dtype == np.int64
+                assert got.tolist() == [at.get(value[q], -1) for q in chosen]
+        kmers, got = ref.class_ids(rows, cols)
+        assert (got >= 0).all() and len(set(got.tolist())) > 2
+        assert np.bincount(got, minlength=len(tally)).tolist() == [0 if v == 0 else n for v, n in sorted(tally.items())]
+        assert (ref.class_ids(rows[::2], cols)[1] < 0).any()
     # the bucketed form of a selection at two geometries
     sel = ref.select(None)
     for n_bits, kb in ((1, 2), (2 * k - 1, 4)):
@@ -202,7 +217,18 @@ def test_fixture_discriminates(case):
     for request in cells.SELECTS:
         got = ref.select(**request)
         assert 0 < got.size < ref.n_distinct, request
-    # the queries and sequences of the GPU test hit, miss and repeat
+    # every class-id request: at least three distinct ids against the full table of its columns, and no id on more
+    # than half of the selection -- a constant id array, or ids that left their keys, cannot pass
+    for request, distinct, largest in zip(cells.CLASS_REQUESTS, (6, 4, 4) if k >= 4 else (5, 3, 3), (0.38, 0.38, 0.5)):
+        kmers, ids = ref.class_ids(ref.color_classes(request["cols"])[0], **request)
+        assert np.array_equal(kmers, ref.select(**request)) and (ids >= 0).all(), request
+        share = np.bincount(ids) / ids.size
+        assert (share > 0).sum() >= 3 and share.max() <= 0.5, (request, share)
+        if cell != cells.DENSE:  # the dealing of PART_OF_RANK: the same classes at every geometry
+            assert (share > 0).sum() == distinct and share.max() <= largest + 0.005, (request, share)
+        # neighbouring keys have different classes somewhere in every bucket that holds several k-mers of several
+        # classes: an id that left its key in a tile's sort shows
+        assert (np.diff(ids) != 0).mean() > 0.3, request
     q = cells.queries_of(ref, plain, seed=k * 31 + n)
     hit = ref.query_rows(q, not plain).any(axis=1)
     assert hit[:ref.n_distinct].all() and not hit[-3:].any()

@@ -5,6 +5,7 @@ import numpy as np
 
 import oracle_lib as ol
 import paint_reference as pr
+from paint_reference import with_zero_row
 from index_reference import IndexReference, class_matrix, revcomp_string
 from kmersets import synth
 
@@ -13,12 +14,6 @@ U = np.uint64
 
 def kmers(*words):
     return np.unique(np.array([synth.kmers_of_bases(synth.bases_of_string(w), len(w))[0] for w in words], dtype=U))
-
-
-def with_zero_row(table):
-    """The table with the zero row, ascending by (high, low)."""
-    t = np.unique(np.concatenate([np.zeros((1, 2), dtype=U), np.asarray(table, dtype=U).reshape(-1, 2)]), axis=0)
-    return t[np.lexsort((t[:, 0], t[:, 1]))]
 
 
 def test_hand_worked():
@@ -82,6 +77,30 @@ def test_runs_expand_to_the_ids_and_adjacent_runs_differ():
     assert off[1] > 3
     first, last = slice(off[0], off[1]), slice(off[-2], off[-1])
     assert np.array_equal(cls[first][::-1], cls[last])
+
+
+def test_a_single_kmer_paints_with_its_class_id():
+    """A K-long string of k-mer q has one run, and its class is IndexReference.class_ids of q under the union
+    selection (-1 where the table does not hold q's row, or no column holds q): the two references agree."""
+    ref, _ = fabricated(7)
+    k = ref.k
+    absent = np.setdiff1d(synth.canonical(np.arange(5000, 5040, dtype=U), k), ref.kmers)[:5]
+    assert absent.size == 5
+    for cols in (None, [4, 1], [2, 0, 3]):
+        rows, _ = ref.color_classes(cols)
+        for table in (rows, rows[1::2], with_zero_row(rows)):
+            kmers, ids = ref.class_ids(table, cols)
+            some = np.concatenate([ref.kmers[::7], absent])
+            strings = ["".join("ACGT"[(int(q) >> (2 * (k - 1 - j))) & 3] for j in range(k)) for q in some]
+            off, start, cls, missing = pr.class_runs(ref, strings, cols, table, True)
+            assert off.tolist() == list(range(len(strings) + 1)) and not start.any()
+            at = np.minimum(np.searchsorted(kmers, some), kmers.size - 1)
+            selected = kmers[at] == some  # (in some column: the union selection holds it)
+            assert selected[:-5].any() and not selected[-5:].any()
+            assert np.array_equal(cls[selected], ids[at[selected]])
+            zero = [c for c, r in enumerate(table.tolist()) if r == [0, 0]]
+            assert (cls[~selected] == (zero[0] if zero else -1)).all()
+            assert missing == int((cls == -1).sum())
 
 
 def test_runs_summed_per_column_are_seq_hits():
