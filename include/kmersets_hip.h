@@ -169,7 +169,7 @@ int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
  * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
  * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
  * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
- * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes, ksh_seq_class_runs and the accessors of a ksh_kss /
+ * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes, ksh_seq_class_runs, ksh_spss_cut and the accessors of a ksh_kss /
  * ksh_kss_index, plans and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
  * plan: nothing else uses their slot.
  *
@@ -873,6 +873,38 @@ typedef struct ksh_seq_paint {
 int ksh_seq_class_runs(const ksh_spss_view* seqs, ksh_kss_index* idx, const ksh_seq_paint* req,
                        int64_t capacity, int64_t* d_run_offsets, uint32_t* d_run_start, uint32_t* d_run_class,
                        int64_t* n_runs, int64_t* n_unmatched);
+
+/* ---- Cutting the strings of a container at runs: coloured unitigs ------------------------------------------------
+ * The strings of an SPSS container cut at given k-mer positions, the K - 1 bases behind every cut repeated: the
+ * k-mers of the output strings in order are the k-mers of the input strings in order, so the k-mer set is unchanged.
+ * Cut at the runs that ksh_seq_class_runs gives for the strings of ksh_spss_encode of the union selection, every output
+ * string is monochromatic -- all its k-mers have one colour class, d_run_class[r] is the class of string r -- which is
+ * the form coloured-graph tools exchange (coloured unitigs and the class table beside them).  Any run list can drive
+ * the call, not only a painting.
+ * Input string s has P_s = lens[s] + 1 positions; pstart is the exclusive scan of P_s, and string s begins at base
+ * pstart[s] + s (K - 1) of the stream.  The run list is d_run_offsets (device int64[n_strings + 1]) and d_run_start
+ * (device uint32[n_runs]) exactly as ksh_seq_class_runs writes them: run r belongs to string s when off[s] <= r <
+ * off[s + 1], and covers positions a = start[r] up to e, e = start[r + 1] if r + 1 < off[s + 1], otherwise P_s.
+ * Output: a container of n_runs strings.  String r is bases [a, e + K - 1) of input string s, and d_lens[r] =
+ * e - a - 1.  Every cut repeats K - 1 bases: n_bases_out = n_bases + (n_runs - n_strings)(K - 1), which the caller
+ * computes to size d_words (ceil(n_bases_out / 32) words) -- there is no plan call; d_lens holds n_runs entries.
+ * Nothing is written outside these two ranges, whatever the inputs.  With q_r = pstart[s] + a, output string r begins
+ * at output base q_r + r (K - 1), and its bases are the input bases at the same index minus (r - s)(K - 1).  The bits
+ * behind base n_bases_out - 1 of the last word are unspecified, as in every container.  *n_bases (host, may be NULL)
+ * receives n_bases_out.
+ * n_strings == 0 requires n_runs == 0: KSH_OK, *n_bases = 0, nothing is read or written on the device.
+ * KSH_INVALID_ARGUMENT, each with a message that names the field.  On the host: NULL seqs, ctx, g or (with strings)
+ * arrays; negative sizes; n_runs < n_strings; a geometry no call accepts; K < 4.  On the device, by one check kernel
+ * and one synchronisation before any output word or length is written, naming the first offending string or run:
+ * off[0] != 0; off[n_strings] != n_runs; off[s] >= off[s + 1]; start[off[s]] != 0; starts not strictly ascending
+ * within a string; a start >= P_s; and what ksh_seq_hits refuses of the container, lens[s] == UINT32_MAX and
+ * sum(lens + K) != n_bases.  The context still serves after any refusal.
+ * The call is stateless like the sequence queries: scratch comes from the context's pool (8 bytes per string, 8 bytes
+ * per run) and is given back before the call returns; it keeps no plan, joins no plan group and ends no pending plan.
+ * It synchronises the context's stream twice: for the checks and at the end.  As with ksh_seq_hits the sequences come
+ * first and the context second. */
+int ksh_spss_cut(const ksh_spss_view* seqs, ksh_ctx* ctx, const ksh_geom* g, const int64_t* d_run_offsets,
+                 const uint32_t* d_run_start, int64_t n_runs, uint64_t* d_words, uint32_t* d_lens, int64_t* n_bases);
 
 #ifdef __cplusplus
 }

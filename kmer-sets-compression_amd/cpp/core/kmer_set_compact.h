@@ -10,6 +10,7 @@
 #ifndef KSC_CORE_KMER_SET_COMPACT_H_
 #define KSC_CORE_KMER_SET_COMPACT_H_
 
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -153,6 +154,29 @@ class KmerSetCompact {
   }
 
   std::int64_t Weight() const { return n_bases_; }
+
+  // The strings cut at k-mer positions (ksh_spss_cut): the runs of string s are runs offsets[s] .. offsets[s + 1),
+  // run r begins at position start[r] of its string (the first run of a string at 0) -- the run list that
+  // KmerSetSetIndex::Paint returns.  Every run becomes a string of its own, the K - 1 bases behind a cut repeated:
+  // the same k-mers in the same order, in offsets.back() strings.
+  KmerSetCompact Cut(const std::vector<std::int64_t>& offsets, const std::vector<std::uint32_t>& start) const {
+    const ksh_geom g = Set::Geom();
+    const ksh_spss_view v = View();
+    KmerSetCompact c;
+    c.n_ = static_cast<std::int64_t>(start.size());
+    if (offsets.size() != std::size_t(n_) + 1) throw std::invalid_argument("Cut: offsets holds n_strings + 1 values");
+    c.n_bases_ = n_bases_ + (c.n_ - n_) * (K - 1);  // (the closed form: the call needs no plan)
+    if (c.n_ < n_) throw std::invalid_argument("Cut: fewer runs than strings");
+    c.words_ = ksc::DeviceBuffer(std::size_t((c.n_bases_ + 31) / 32) * 8);
+    c.lens_ = ksc::DeviceBuffer(start.size() * 4);
+    const ksc::DeviceBuffer d_off = ksc::DeviceBuffer::FromHost(offsets);
+    const ksc::DeviceBuffer d_start = ksc::DeviceBuffer::FromHost(start);
+    ksc::Check(ksh_spss_cut(&v, ksc::Ctx(), &g, static_cast<const std::int64_t*>(d_off.get()),
+                            static_cast<const std::uint32_t*>(d_start.get()), c.n_,
+                            static_cast<std::uint64_t*>(c.words_.get()), static_cast<std::uint32_t*>(c.lens_.get()),
+                            &c.n_bases_));
+    return c;
+  }
 
   // bucket_ids[i] = j  <->  result[i] holds the sorted keys of bucket j.
   std::vector<std::vector<KeyType>> GetSampledKmerSet(const std::vector<int>& bucket_ids, bool canonical,

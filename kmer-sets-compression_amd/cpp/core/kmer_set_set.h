@@ -490,6 +490,27 @@ class KmerSetSetIndex {
                  capacity);
   }
 
+  // The coloured de Bruijn graph of `cols` as monochromatic strings (coloured unitigs): `strings` holds every k-mer
+  // that a column holds exactly once, all k-mers of string r have the membership pattern classes[cls[r]] over cols,
+  // and `classes` is ColorClasses(cols).  The union selection is encoded (KmerSetCompact::FromKmerSet), painted
+  // (Paint) and cut at the runs (KmerSetCompact::Cut, ksh_spss_cut).  canonical: as the structure was built.
+  struct ColoredStrings {
+    KmerSetCompact<K, N, KeyType> strings;
+    std::vector<std::uint32_t> cls;
+    std::vector<ColorClass> classes;
+  };
+  ColoredStrings ColoredUnitigs(const std::vector<int>& cols, bool canonical = true) const {
+    ColoredStrings out;
+    out.classes = ColorClasses(cols);
+    const KmerSet<K, N, KeyType> all = SelectClasses(cols, out.classes).first;
+    if (all.Size() == 0) return out;
+    const auto uncut = KmerSetCompact<K, N, KeyType>::FromKmerSet(all, canonical, true, 1);
+    ClassRuns runs = Paint(uncut, cols, out.classes, canonical, false);
+    out.strings = uncut.Cut(runs.offsets, runs.start);
+    out.cls = std::move(runs.cls);
+    return out;
+  }
+
  private:
   static ksh_kss_selection Selection(const std::vector<std::int32_t>& ids, int min_count, int max_count,
                                      const std::vector<std::int32_t>& req, const std::vector<std::int32_t>& exc) {

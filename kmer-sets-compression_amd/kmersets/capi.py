@@ -208,6 +208,7 @@ def lib():
                                             C.POINTER(i64)]),
         "ksh_seq_class_runs": (C.c_int, [C.POINTER(SpssView), vp, C.POINTER(SeqPaint), i64, vp, vp, vp, C.POINTER(i64),
                                          C.POINTER(i64)]),
+        "ksh_spss_cut": (C.c_int, [C.POINTER(SpssView), vp, GP, vp, vp, i64, vp, vp, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -672,6 +673,32 @@ class Context:
         mode 2: GetSPSSCanonical(fast = false).  Returns a DeviceSpss."""
         return self.spss_encode_write(self.spss_encode_plan(s, mode, canonical))
 
+    def spss_cut(self, seqs, run_offsets, run_start):
+        """ksh_spss_cut: the strings of `seqs` (a DeviceSpss) cut at the runs (run_offsets int64[n_strings + 1],
+        run_start int32 or uint32 [n_runs], device tensors as KssIndex.class_runs returns them; n_runs is the size of
+        run_start) into one string per run, K - 1 bases repeated at every cut: the same k-mers in the same order.
+        Returns a DeviceSpss of n_runs strings."""
+        import torch
+
+        with torch.cuda.stream(self.stream):
+            n, n_runs = seqs.n_strings, int(run_start.numel())
+            off = run_offsets.contiguous()
+            if off.dtype != torch.int64 or off.numel() != n + 1:
+                raise ValueError("run_offsets: int64[n_strings + 1] = int64[%d] wanted, %s[%d] given"
+                                 % (n + 1, off.dtype, off.numel()))
+            start = run_start.contiguous()
+            if start.element_size() != 4 or start.is_floating_point():
+                raise ValueError("run_start: int32 or uint32 wanted, %s given" % start.dtype)
+            n_out = seqs.n_bases + (n_runs - n) * (seqs.g.k - 1)  # (the closed form: no plan call)
+            words = torch.empty(max((max(n_out, 0) + 31) // 32, 1), dtype=torch.int64, device=self.device)
+            lens = torch.empty(max(n_runs, 1), dtype=torch.int32, device=self.device)
+            view, got = seqs.view(), C.c_int64()
+            check(lib().ksh_spss_cut(C.byref(view), self.h, C.byref(seqs.g), off.data_ptr(),
+                                     start.data_ptr() if n_runs else None, n_runs, words.data_ptr(), lens.data_ptr(),
+                                     C.byref(got)))
+            assert got.value == n_out
+            return DeviceSpss(seqs.g, words, lens, n_runs, n_out)
+
     def spss_encode_stats(self):
         st = (C.c_int64 * 4)()
         check(lib().ksh_spss_encode_stats(self.h, st))
@@ -855,6 +882,7 @@ class DeviceKmerSetSet:
         lives on one rank (node_holder).  g: the geometry, needed only where there is no input to
         take it from (no inputs at all: a structure of 0 nodes)."""
         self.ctx, self.g, self.inputs = ctx, g if g is not None else compacts[0].g, list(compacts)
+        self.canonical = bool(canonical)
         views = (SpssView * max(len(compacts), 1))(*[c.view() for c in compacts])
         ids = np.ascontiguousarray(bucket_ids, dtype=np.int32)
         h = C.c_void_p()
@@ -1021,8 +1049,9 @@ CLASS_NONE = 0xFFFFFFFF  # KSH_CLASS_NONE: the id of a k-mer whose row the class
 class KssIndex:
     """ksh_kss_index: which nodes' Get(i) hold each query k-mer (kmer_set_set.h:433-454), for every node i."""
 
-    def __init__(self, ctx, h, keep, borrowed=None, g=None):
+    def __init__(self, ctx, h, keep, borrowed=None, g=None, canonical=True):
         self.ctx, self.h, self._keep, self._borrowed, self.g = ctx, h, keep, borrowed, g
+        self.canonical = bool(canonical)  # (what the node sets were decoded with: colored_unitigs encodes with it)
         n, w, b = C.c_int32(), C.c_int32(), C.c_int64()
         check(lib().ksh_kss_index_info(h, C.byref(n), C.byref(w), C.byref(b)))
         self.n_nodes, self.words = n.value, w.value
@@ -1032,7 +1061,7 @@ class KssIndex:
         """Borrows the resident node sets of a built DeviceKmerSetSet (kept alive by the index)."""
         h = C.c_void_p()
         check(lib().ksh_kss_index_from_kss(dkss.h, C.byref(h)))
-        return cls(dkss.ctx, h, dkss, borrowed=dkss, g=dkss.g)
+        return cls(dkss.ctx, h, dkss, borrowed=dkss, g=dkss.g, canonical=getattr(dkss, "canonical", True))
 
     def _handle(self):
         """The live index; an index whose borrowed structure was closed is closed too (its node sets are gone)."""
@@ -1058,7 +1087,7 @@ class KssIndex:
         check(lib().ksh_kss_index_create(ctx.h, C.byref(compacts[0].g if n else Geom()), views, n,
                                           offs.ctypes.data_as(C.POINTER(C.c_int64)),
                                           ids.ctypes.data_as(C.POINTER(C.c_int32)), int(canonical), C.byref(h)))
-        return cls(ctx, h, list(compacts), g=compacts[0].g if n else None)
+        return cls(ctx, h, list(compacts), g=compacts[0].g if n else None, canonical=canonical)
 
     def query(self, kmers, canonicalize=True, route=0, packed=False):
         """Rows for the 2K-bit patterns `kmers` (numpy, or a device torch tensor of int64/uint64): an n x n_nodes
@@ -1357,6 +1386,26 @@ class KssIndex:
         out = self.class_runs(seqs, rows, cols, canonicalize, route, pass_positions, None, allow_unmatched)
         return out + (rows, counts)
 
+    def colored_unitigs(self, cols=None, mode=0, route=0, pass_positions=0):
+        """The coloured de Bruijn graph of the columns as monochromatic strings: (spss, string_class, rows, counts).
+        spss is a DeviceSpss whose strings hold every k-mer that a column holds exactly once, all k-mers of a string
+        in one colour class; string_class is a device int32 tensor [n_strings], string r has class string_class[r] of
+        the table rows, counts = color_classes(cols).  The union selection with its classes (select_classes) is
+        encoded (Context.spss_encode with `mode` and the index's canonical flag), the strings are painted
+        (class_runs with `route` and `pass_positions`) and cut at the runs (Context.spss_cut); nothing but the counts
+        those calls return leaves the device."""
+        ds, _, rows, counts = self.select_classes(cols)
+        if ds.n_keys == 0:
+            import torch
+
+            with torch.cuda.stream(self.ctx.stream):
+                none = torch.zeros(0, dtype=torch.int32, device=self.ctx.device)
+            return DeviceSpss.from_strings(self.g, [], self.ctx.device), none, rows, counts
+        uncut = self.ctx.spss_encode(ds, mode=mode, canonical=self.canonical)
+        off, start, cls, _ = self.class_runs(uncut, rows, cols, canonicalize=self.canonical, route=route,
+                                             pass_positions=pass_positions, allow_unmatched=False)
+        return self.ctx.spss_cut(uncut, off, start), cls, rows, counts
+
     @staticmethod
     def class_matrix(rows, n_cols):
         """bool[n, n_cols] of the rows color_classes returned: element [c, a] is bit a of class c."""
@@ -1502,6 +1551,7 @@ class OwnedKmerSetSet(DeviceKmerSetSet):
         if not mine and g is None:
             raise ValueError("rank %d owns no input: pass the geometry (g=)" % self.rank)
         self.g, self.inputs = g if g is not None else mine[0].g, list(compacts)
+        self.canonical = bool(canonical)
         for i, c in enumerate(compacts):
             if (c is not None) != (self.owners[i] == self.rank):
                 raise ValueError("input %d: the container must be given on its owner (rank %d) only" % (i, self.owners[i]))
