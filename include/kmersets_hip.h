@@ -169,7 +169,7 @@ int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
  * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
  * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
  * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
- * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes, ksh_seq_class_runs, ksh_spss_cut and the accessors of a ksh_kss /
+ * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes, ksh_seq_class_runs, ksh_spss_cut, ksh_spss_links and the accessors of a ksh_kss /
  * ksh_kss_index, plans and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
  * plan: nothing else uses their slot.
  *
@@ -905,6 +905,47 @@ int ksh_seq_class_runs(const ksh_spss_view* seqs, ksh_kss_index* idx, const ksh_
  * first and the context second. */
 int ksh_spss_cut(const ksh_spss_view* seqs, ksh_ctx* ctx, const ksh_geom* g, const int64_t* d_run_offsets,
                  const uint32_t* d_run_start, int64_t n_runs, uint64_t* d_words, uint32_t* d_lens, int64_t* n_bases);
+
+/* ---- The links between the strings of a container: the edges of the graph -----------------------------------------
+ * The strings of an SPSS container as the nodes of a graph, and its edges (GFA: S lines, and L lines with a (K-1)M
+ * overlap).  The container has n strings over ACGT whose k-mers are all distinct.
+ * The oriented string v = 2 s + o is string s as written (o = 0) or its reverse complement (o = 1); first(v) and
+ * last(v) are its first and last k-mer, first(2 s + 1) = rc(last(2 s)).
+ * canonical != 0: for each base b of ACGT in this order let y = last(v)[1:] + b.  If canon(y) == canon(last(v)) the
+ * base is skipped; otherwise v -> w is a link iff first(w) == y.  canonical == 0: only the vertices with o = 0 exist,
+ * a base is skipped when y == last(v), and the rows 2 s + 1 are empty.
+ * Skipped, then, is a k-mer followed by itself: the one-k-mer loop AAAAA -> AAAAA and the hairpin x -> rc(x) of a K - 1
+ * overlap that is its own reverse complement (the unitig walk of ksh_spss_encode ignores both as well).  A circular
+ * string of two or more k-mers does link to itself (v -> v).
+ * Output, in CSR form: d_link_offsets (device int64[2 n + 1], may be NULL; written whenever given) and d_link_to
+ * (device int64[capacity]): the links of v are entries off[v] .. off[v + 1) of d_link_to, ascending by b.  A base
+ * reaches at most one w, so a row has at most 4 entries and n_links <= 8 n.  In canonical mode v -> w iff
+ * w ^ 1 -> v ^ 1: both twins are listed.
+ * ONLY STRING ENDS ARE LOOKED AT: an extension that lands inside a string is no link.  When the strings are the
+ * unitigs of their k-mer set (ksh_spss_encode, mode 1) or any cut of them (ksh_spss_cut), the k-mer pairs
+ * (last(v), first(w)) of the links together with the consecutive k-mer pairs inside the oriented strings are exactly
+ * the edges x -> y with canon(x) != canon(y) of the set's node-centric de Bruijn graph, and the two parts are
+ * disjoint.  For other containers -- a mode-0 path cover, say -- the links are the edges between string ends only.
+ * *n_links (host, required) is always the true number.  capacity == 0 counts only: d_link_to may be NULL and is not
+ * touched.  n_links > capacity > 0: KSH_FAILED_PRECONDITION with a message that names capacity and gives n_links;
+ * d_link_to is then untouched (the offsets, if given, are whole).  Nothing is ever written at or beyond capacity, or
+ * beyond 2 n + 1 offsets.
+ * n_strings == 0: KSH_OK, *n_links = 0, d_link_offsets[0] = 0 if given; nothing else touches the device.
+ * KSH_INVALID_ARGUMENT, each with a message that names the field.  On the host: NULL seqs, ctx, g or n_links;
+ * negative sizes, NULL words or lens with strings; a geometry no call accepts; K < 4; a negative capacity; a NULL
+ * d_link_to with capacity > 0.  On the device, before any output element is written, naming the smallest offending
+ * string: what ksh_seq_hits refuses of the container, lens[s] == UINT32_MAX and sum(lens + K) != n_bases (before the
+ * words are read); two string ends with the same end k-mer (after canonicalisation in canonical mode) -- the two ends
+ * of a one-k-mer string are one end and are fine, a longer string whose first and last k-mer coincide is refused; in
+ * canonical mode an end k-mer that is its own reverse complement (even K only; ksh_spss_encode refuses such sets
+ * too).  The context still serves after any refusal.
+ * The call is stateless like ksh_spss_cut: scratch comes from the context's pool (40 bytes per string, and 16 bytes
+ * per slot of an end table of the next power of two >= 4 n slots) and is given back before the call returns; it keeps
+ * no plan, joins no plan group and ends no pending plan.  It synchronises the context's stream three times: for the
+ * container's sizes, for the end check and the count, and at the end.  A row is a function of the container alone.
+ * As with ksh_spss_cut the sequences come first and the context second. */
+int ksh_spss_links(const ksh_spss_view* seqs, ksh_ctx* ctx, const ksh_geom* g, int canonical, int64_t capacity,
+                   int64_t* d_link_offsets, int64_t* d_link_to, int64_t* n_links);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,23 @@ class KmerSetCompact {
     return c;
   }
 
+  // The unitigs of the set as a container (GetUnitigsCanonical / GetUnitigs kept on the device: ksh_spss_encode,
+  // mode 1).  Links() of it, or of any Cut of it, is the whole de Bruijn graph of the set.
+  static KmerSetCompact UnitigsOf(const Set& kmer_set, bool canonical) {
+    const ksh_geom g = Set::Geom();
+    const ksh_set_view v = kmer_set.View();
+    KmerSetCompact c;
+    ksc::Check(ksh_spss_encode_plan(ksc::Ctx(), &g, &v, canonical ? 1 : 0, 1, &c.n_, &c.n_bases_));
+    c.words_ = ksc::DeviceBuffer(std::size_t((c.n_bases_ + 31) / 32) * 8);
+    c.lens_ = ksc::DeviceBuffer(std::size_t(c.n_) * 4);
+    ksc::Check(ksh_spss_encode_write_for(ksc::Ctx(), static_cast<std::uint64_t*>(c.words_.get()),
+                                         static_cast<std::uint32_t*>(c.lens_.get()), c.n_, c.n_bases_,
+                                         v.d_offsets));
+    ksc::Check(ksh_ctx_sync(ksc::Ctx()));
+    ksc::Check(ksh_spss_encode_release(ksc::Ctx()));
+    return c;
+  }
+
   // From SPSS strings over ACGT (the reference's private constructor, :206-266).
   static KmerSetCompact FromStrings(const std::vector<std::string>& spss) {
     KmerSetCompact c;
@@ -176,6 +193,32 @@ class KmerSetCompact {
                             static_cast<std::uint64_t*>(c.words_.get()), static_cast<std::uint32_t*>(c.lens_.get()),
                             &c.n_bases_));
     return c;
+  }
+
+  // The links between the strings (ksh_spss_links), the edges of the graph whose nodes they are.  The oriented
+  // string v = 2 s + o is string s as written (o = 0) or reverse-complemented (o = 1); v -> w is a link when the last
+  // k-mer of v moved on by one base is the first k-mer of w, a k-mer followed by itself (canonical: or by its reverse
+  // complement) excepted.  The links of v are to[offsets[v]] .. to[offsets[v + 1]), ascending by the appended base;
+  // canonical == false: only the rows 2 s have any.  Only string ends are looked at.
+  struct LinkList {
+    std::vector<std::int64_t> offsets, to;
+  };
+  LinkList Links(bool canonical = true) const {
+    const ksh_geom g = Set::Geom();
+    const ksh_spss_view v = View();
+    LinkList out;
+    std::int64_t n_links = 0;
+    ksc::DeviceBuffer off(std::size_t(2 * n_ + 1) * 8);
+    ksc::Check(ksh_spss_links(&v, ksc::Ctx(), &g, canonical ? 1 : 0, 0, static_cast<std::int64_t*>(off.get()), nullptr,
+                              &n_links));
+    out.offsets = off.ToHost<std::int64_t>(std::size_t(2 * n_ + 1));
+    if (n_links > 0) {
+      ksc::DeviceBuffer to(std::size_t(n_links) * 8);
+      ksc::Check(ksh_spss_links(&v, ksc::Ctx(), &g, canonical ? 1 : 0, n_links, nullptr,
+                                static_cast<std::int64_t*>(to.get()), &n_links));
+      out.to = to.ToHost<std::int64_t>(std::size_t(n_links));
+    }
+    return out;
   }
 
   // bucket_ids[i] = j  <->  result[i] holds the sorted keys of bucket j.

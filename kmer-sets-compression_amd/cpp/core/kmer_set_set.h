@@ -511,6 +511,29 @@ class KmerSetSetIndex {
     return out;
   }
 
+  // The coloured compacted de Bruijn graph of `cols`, nodes and edges: as ColoredUnitigs, but the union selection is
+  // encoded as unitigs (KmerSetCompact::UnitigsOf), so that the strings are pieces of unitigs and `links`
+  // (KmerSetCompact::Links of them, ksh_spss_links) holds every edge of the graph.
+  struct ColoredGraphResult {
+    KmerSetCompact<K, N, KeyType> strings;
+    std::vector<std::uint32_t> cls;
+    std::vector<ColorClass> classes;
+    typename KmerSetCompact<K, N, KeyType>::LinkList links;
+  };
+  ColoredGraphResult ColoredGraph(const std::vector<int>& cols, bool canonical = true) const {
+    ColoredGraphResult out;
+    out.classes = ColorClasses(cols);
+    out.links.offsets.assign(1, 0);
+    const KmerSet<K, N, KeyType> all = SelectClasses(cols, out.classes).first;
+    if (all.Size() == 0) return out;
+    const auto uncut = KmerSetCompact<K, N, KeyType>::UnitigsOf(all, canonical);
+    ClassRuns runs = Paint(uncut, cols, out.classes, canonical, false);
+    out.strings = uncut.Cut(runs.offsets, runs.start);
+    out.cls = std::move(runs.cls);
+    out.links = out.strings.Links(canonical);
+    return out;
+  }
+
  private:
   static ksh_kss_selection Selection(const std::vector<std::int32_t>& ids, int min_count, int max_count,
                                      const std::vector<std::int32_t>& req, const std::vector<std::int32_t>& exc) {

@@ -209,6 +209,7 @@ def lib():
         "ksh_seq_class_runs": (C.c_int, [C.POINTER(SpssView), vp, C.POINTER(SeqPaint), i64, vp, vp, vp, C.POINTER(i64),
                                          C.POINTER(i64)]),
         "ksh_spss_cut": (C.c_int, [C.POINTER(SpssView), vp, GP, vp, vp, i64, vp, vp, C.POINTER(i64)]),
+        "ksh_spss_links": (C.c_int, [C.POINTER(SpssView), vp, GP, C.c_int, i64, vp, vp, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -242,6 +243,39 @@ def geom(k, n_bucket_bits, key_bytes=None):
 
 
 KEY_DTYPE = {2: np.uint16, 4: np.uint32, 8: np.uint64}
+
+
+def gfa_lines(strings, k, link_offsets, link_to, string_class=None):
+    """GFA 1 text of a graph of strings, a list of lines without newlines: the header H\tVN:Z:1.0, a segment line
+    S\t<r>\t<seq> per string (with \tCL:i:<class> when string_class is given) and a link line
+    L\t<a>\t<+|->\t<b>\t<+|->\t<K-1>M for every link 2 a + (orientation -) -> 2 b + (orientation -) of
+    link_offsets / link_to as Context.spss_links returns them (tensors, arrays or lists).  Every link is written: in
+    canonical mode that is both twins, a -> b and the reverse complement of b -> the reverse complement of a."""
+    def host(x):
+        return np.asarray(x.cpu() if hasattr(x, "cpu") else x).reshape(-1)
+
+    off, to = host(link_offsets).astype(np.int64), host(link_to).astype(np.int64)
+    cls = None if string_class is None else host(string_class).astype(np.int64)
+    n = len(strings)
+    if off.size != 2 * n + 1 or (cls is not None and cls.size != n):
+        raise ValueError("gfa_lines: %d strings need %d offsets (and %d classes)" % (n, 2 * n + 1, n))
+    lines = ["H\tVN:Z:1.0"]
+    for r, s in enumerate(strings):
+        lines.append("S\t%d\t%s" % (r, s) + ("" if cls is None else "\tCL:i:%d" % cls[r]))
+    overlap = "%dM" % (int(k) - 1)
+    for v in range(2 * n):
+        for w in to[off[v]:off[v + 1]]:
+            lines.append("L\t%d\t%s\t%d\t%s\t%s" % (v >> 1, "-" if v & 1 else "+", int(w) >> 1,
+                                                    "-" if int(w) & 1 else "+", overlap))
+    return lines
+
+
+def write_gfa(path, strings, k, link_offsets, link_to, string_class=None):
+    """gfa_lines written to `path`, a newline behind every line.  Returns the number of lines."""
+    lines = gfa_lines(strings, k, link_offsets, link_to, string_class)
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return len(lines)
 
 
 class DeviceSet:
@@ -698,6 +732,43 @@ class Context:
                                      C.byref(got)))
             assert got.value == n_out
             return DeviceSpss(seqs.g, words, lens, n_runs, n_out)
+
+    def spss_links_raw(self, seqs, canonical, capacity, offsets=None, link_to=None):
+        """ksh_spss_links, one call: (rc, n_links).  offsets, link_to: device int64 tensors or None.  rc is KSH_OK or
+        KSH_FAILED_PRECONDITION (too small a capacity: the message is ksh_last_error); anything else is raised."""
+        import torch
+
+        with torch.cuda.stream(self.stream):
+            view, n = seqs.view(), C.c_int64(-1)
+            rc = lib().ksh_spss_links(C.byref(view), self.h, C.byref(seqs.g), int(bool(canonical)), int(capacity),
+                                      offsets.data_ptr() if offsets is not None else None,
+                                      link_to.data_ptr() if link_to is not None else None, C.byref(n))
+            if rc not in (KSH_OK, KSH_FAILED_PRECONDITION):
+                check(rc)
+            return rc, n.value
+
+    def spss_links(self, seqs, canonical=True):
+        """ksh_spss_links: the links between the strings of `seqs` (a DeviceSpss), the edges of the graph whose nodes
+        the strings are.  The oriented string v = 2 s + o is string s as written (o = 0) or reverse-complemented
+        (o = 1); v -> w is a link when the last k-mer of v moved on by one base is the first k-mer of w (a k-mer
+        followed by itself, or with `canonical` by its reverse complement, is none).  Returns (link_offsets, link_to),
+        device int64 tensors [2 n + 1] and [n_links]: the links of v are link_to[link_offsets[v]:link_offsets[v + 1]],
+        ascending by the appended base.  canonical False: only the rows 2 s have links.  Only string ends are looked
+        at; on unitigs or cuts of them (spss_encode mode 1, spss_cut) that is the whole graph.  One call counts, a
+        second one fills."""
+        import torch
+
+        with torch.cuda.stream(self.stream):
+            off = torch.zeros(2 * seqs.n_strings + 1, dtype=torch.int64, device=self.device)
+        rc, n_links = self.spss_links_raw(seqs, canonical, 0, off)
+        check(rc)
+        with torch.cuda.stream(self.stream):
+            link_to = torch.empty(max(n_links, 1), dtype=torch.int64, device=self.device)
+        if n_links:
+            rc, again = self.spss_links_raw(seqs, canonical, n_links, off, link_to)
+            check(rc)
+            assert again == n_links
+        return off, link_to[:n_links]
 
     def spss_encode_stats(self):
         st = (C.c_int64 * 4)()
@@ -1405,6 +1476,15 @@ class KssIndex:
         off, start, cls, _ = self.class_runs(uncut, rows, cols, canonicalize=self.canonical, route=route,
                                              pass_positions=pass_positions, allow_unmatched=False)
         return self.ctx.spss_cut(uncut, off, start), cls, rows, counts
+
+    def colored_graph(self, cols=None, route=0, pass_positions=0):
+        """The coloured compacted de Bruijn graph of the columns, nodes and edges: (spss, string_class, rows, counts,
+        link_offsets, link_to).  The first four are colored_unitigs(cols, mode=1, route, pass_positions): mode 1 makes
+        the strings pieces of unitigs, so the links between their ends are all the edges of the graph.  The last two
+        are Context.spss_links of those strings with the index's canonical flag."""
+        spss, cls, rows, counts = self.colored_unitigs(cols, mode=1, route=route, pass_positions=pass_positions)
+        off, link_to = self.ctx.spss_links(spss, canonical=self.canonical)
+        return spss, cls, rows, counts, off, link_to
 
     @staticmethod
     def class_matrix(rows, n_cols):
