@@ -169,7 +169,7 @@ int ksh_ctx_timing_wall(ksh_ctx* ctx, int kind, float* wall_ms);
  * ksh_pair_algebra, ksh_pair_algebra_batch, ksh_dsu_components, both StreamVByte calls, ksh_spss_size,
  * ksh_spss_to_text, the copies, ksh_ctx_reserve (the plans keep nothing in the arena), the timing and memory
  * calls, ksh_ctx_set_lanes, ksh_kss_index_query, ksh_seq_hits, ksh_kss_pair_counts, ksh_kss_select_count,
- * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes, ksh_seq_class_runs, ksh_spss_cut, ksh_spss_links and the accessors of a ksh_kss /
+ * ksh_kss_select_keys, ksh_kss_select_class_ids, ksh_kss_color_classes, ksh_seq_class_runs, ksh_spss_cut, ksh_spss_links, ksh_link_bubbles and the accessors of a ksh_kss /
  * ksh_kss_index, plans and writes of another group, and anything done on a different context.  Only a plan of its own group ends a text or FASTA
  * plan: nothing else uses their slot.
  *
@@ -946,6 +946,73 @@ int ksh_spss_cut(const ksh_spss_view* seqs, ksh_ctx* ctx, const ksh_geom* g, con
  * As with ksh_spss_cut the sequences come first and the context second. */
 int ksh_spss_links(const ksh_spss_view* seqs, ksh_ctx* ctx, const ksh_geom* g, int canonical, int64_t capacity,
                    int64_t* d_link_offsets, int64_t* d_link_to, int64_t* n_links);
+
+/* ---- The bubbles of a link graph: variant sites and the sets on each arm -------------------------------------------
+ * The input is the link graph as ksh_spss_links writes it in CANONICAL mode: n strings, 2 n oriented strings
+ * v = 2 s + o, d_link_offsets[2 n + 1], d_link_to[n_links], rows of at most four distinct targets, twin-symmetric
+ * (v -> w iff w ^ 1 -> v ^ 1).  out(v) is the row of v and outdeg(v) its length; indeg(v) := outdeg(v ^ 1), by twin
+ * symmetry the number of links into v.
+ * The walk of arm i (i = 0, 1, in row order) from a source v with outdeg(v) == 2:
+ *     x = out(v)[i]; arm = []
+ *     loop:
+ *       if indeg(x) != 1 or outdeg(x) != 1 or len(arm) == max_arm: the arm fails
+ *       arm.append(x)
+ *       x = out(x)[0]
+ *       if indeg(x) == 2: sink_i = x; stop
+ * A next x with indeg 1 is met again at the top of the loop; any other indeg makes the arm fail there.
+ * v is the source of a bubble (v, w, arm_0, arm_1) iff both arms succeed and sink_0 == sink_1 =: w.  The definition
+ * imposes nothing else: w may branch on (outdeg(w) is free; bubbles back to back share a node), w may be v ^ 1 (a
+ * hairpin bubble), and a ring of one-in one-out strings ends at max_arm.  The two arms cannot merge before the sink:
+ * their first strings differ, because row entries are distinct, and every arm string has indeg 1.
+ * Every bubble has a twin: source w ^ 1, sink v ^ 1, arms reversed and flipped.  A bubble is reported iff
+ * v <= w ^ 1, so once.  The output ascends by v; a source has at most one bubble, so that is a total order.  Arm 0 is
+ * the arm of the lower base, which is row order.
+ * With classes (d_string_class[n] the class of each string, rows the class table, 128 bits a class) the carriers of
+ * an arm are the AND of rows[d_string_class[x >> 1]] over its strings: the sets that hold every k-mer of the allele.
+ * A SET THAT HOLDS ONLY PART OF AN ARM IS NOT A CARRIER.
+ * The arms are chains because ksh_spss_cut cuts unitigs wherever the class changes: an arm that a partly covering set
+ * enters or leaves is several strings, each with one link in and one out.  Nested and multi-allelic sites (a source
+ * of outdeg 3, a bubble inside an arm of another) are no bubbles of this definition.
+ * The result is a function of the graph alone.
+ * Outputs: bubble b has source d_bubble_ends[2 b] and sink d_bubble_ends[2 b + 1]; its arm i is entries
+ * d_arm_offsets[2 b + i] .. d_arm_offsets[2 b + i + 1] of d_arm_strings, oriented strings in walk order; the
+ * carriers of that arm are the two words d_arm_rows[2 (2 b + i)], [.. + 1].
+ * *n_bubbles and *n_arm_strings (host, required) are always the true numbers.  capacity == 0 counts only: the output
+ * pointers may be NULL and nothing is written.  capacity > 0 with n_bubbles > capacity or n_arm_strings >
+ * arm_capacity: KSH_FAILED_PRECONDITION with a message that names the capacity and gives the number; all four
+ * outputs stay untouched.  Nothing is ever written at or beyond a capacity (2 capacity ends, 2 capacity + 1 offsets,
+ * arm_capacity strings, 4 capacity row words).  No bubbles with capacity > 0: d_arm_offsets[0] = 0.
+ * n_strings == 0: KSH_OK, both counts 0, d_arm_offsets[0] = 0 with capacity > 0; nothing else touches the device.
+ * KSH_INVALID_ARGUMENT, each with a message that names the field.  On the host: NULL graph, ctx, n_bubbles or
+ * n_arm_strings; a struct_size smaller than the struct; negative sizes; NULL offsets with strings; NULL d_link_to
+ * with n_links > 0; n_links > 8 n; max_arm outside [1, KSH_BUBBLE_MAX_ARM]; a negative capacity; with capacity > 0 a
+ * NULL d_bubble_ends or d_arm_offsets, a NULL d_arm_strings with arm_capacity > 0; exactly one of d_string_class /
+ * rows; with classes n_classes outside [1, 2^24]; d_arm_rows given without classes, or missing with classes when
+ * capacity > 0.  On the device, before any walk and before any output element is written, each kind with its smallest
+ * offending vertex or link, the offsets first: off[0] != 0; off[2 n] != n_links; off[v] > off[v + 1]; a row longer
+ * than 4; a target outside [0, 2 n); a repeated target in a row; a link v -> w whose twin w ^ 1 -> v ^ 1 is missing
+ * (so the links of ksh_spss_links in non-canonical mode are refused as soon as there is one: canonical links are what
+ * the call takes); a class outside [0, n_classes).  The arrays are the caller's: no kernel reads outside them
+ * whatever they contain, and a malformed graph ends in a refusal.  The context still serves after any refusal.
+ * Stateless like ksh_spss_links: scratch comes from the context's pool (50 bytes per string, 16 bytes per class) and
+ * goes back before the call returns; it keeps no plan, joins no plan group and ends no pending plan.  At most three
+ * synchronisations: the check, the counts, the end.  The graph comes first and the context second. */
+#define KSH_BUBBLE_MAX_ARM 64
+
+typedef struct ksh_link_graph {
+  size_t struct_size;
+  int64_t n_strings;             /* n; the CSR has 2 n rows */
+  const int64_t* d_link_offsets; /* device int64[2 n + 1] */
+  const int64_t* d_link_to;      /* device int64[n_links] */
+  int64_t n_links;
+  const int32_t* d_string_class; /* device int32[n], or NULL */
+  const uint64_t* rows;          /* HOST uint64[2 * n_classes] as ksh_seq_paint, or NULL; both or neither */
+  int64_t n_classes;
+} ksh_link_graph;
+
+int ksh_link_bubbles(const ksh_link_graph* graph, ksh_ctx* ctx, int32_t max_arm, int64_t capacity,
+                     int64_t arm_capacity, int64_t* d_bubble_ends, int64_t* d_arm_offsets, int64_t* d_arm_strings,
+                     uint64_t* d_arm_rows, int64_t* n_bubbles, int64_t* n_arm_strings);
 
 #ifdef __cplusplus
 }

@@ -221,6 +221,52 @@ class KmerSetCompact {
     return out;
   }
 
+  // The bubbles of a link graph (ksh_link_bubbles) over the vectors Links(true) returns: a source v with two links,
+  // two arms of at most max_arm strings each -- every arm string has one link in and one out -- and the sink w where
+  // both arms end.  Each bubble is listed once, as the twin with v <= w ^ 1, ascending by v: bubble b has source
+  // ends[2 b] and sink ends[2 b + 1], and its arm i (arm 0: the lower base) is arm_strings[arm_offsets[2 b + i]] ..
+  // [arm_offsets[2 b + i + 1]), oriented strings in walk order.  With `classes` (the class of every string) and
+  // `rows` (the class table, two words a class) arm_rows holds two words an arm: the AND of the rows of its strings'
+  // classes, the columns that hold every k-mer of the allele (a column that holds only part of an arm is not a
+  // carrier); without both it stays empty.  Only canonical links are taken: a link without its twin is refused.
+  struct BubbleList {
+    std::vector<std::int64_t> ends, arm_offsets, arm_strings;
+    std::vector<std::uint64_t> arm_rows;
+    std::size_t Size() const { return ends.size() / 2; }
+  };
+  static BubbleList LinkBubbles(const std::vector<std::int64_t>& offsets, const std::vector<std::int64_t>& to,
+                                int max_arm = 8, const std::vector<std::uint32_t>& classes = {},
+                                const std::vector<std::uint64_t>& rows = {}) {
+    const bool colored = !classes.empty() || !rows.empty();
+    const ksc::DeviceBuffer d_off = ksc::DeviceBuffer::FromHost(offsets), d_to = ksc::DeviceBuffer::FromHost(to);
+    const ksc::DeviceBuffer d_cls = ksc::DeviceBuffer::FromHost(classes);
+    ksh_link_graph graph{};
+    graph.struct_size = sizeof(graph);
+    graph.n_strings = offsets.empty() ? 0 : std::int64_t(offsets.size() - 1) / 2;
+    graph.d_link_offsets = static_cast<const std::int64_t*>(d_off.get());
+    graph.d_link_to = static_cast<const std::int64_t*>(d_to.get());
+    graph.n_links = std::int64_t(to.size());
+    graph.d_string_class = classes.empty() ? nullptr : static_cast<const std::int32_t*>(d_cls.get());
+    graph.rows = rows.empty() ? nullptr : rows.data();
+    graph.n_classes = std::int64_t(rows.size() / 2);
+    BubbleList out;
+    std::int64_t n_bubbles = 0, n_arm = 0;
+    ksc::Check(ksh_link_bubbles(&graph, ksc::Ctx(), max_arm, 0, 0, nullptr, nullptr, nullptr, nullptr, &n_bubbles,
+                                &n_arm));
+    out.arm_offsets.assign(1, 0);
+    if (n_bubbles == 0) return out;
+    const std::size_t nb = std::size_t(n_bubbles), na = std::size_t(n_arm);
+    ksc::DeviceBuffer ends(2 * nb * 8), arm_off((2 * nb + 1) * 8), arm(na * 8), arm_rows(colored ? 4 * nb * 8 : 0);
+    ksc::Check(ksh_link_bubbles(&graph, ksc::Ctx(), max_arm, n_bubbles, n_arm, static_cast<std::int64_t*>(ends.get()),
+                                static_cast<std::int64_t*>(arm_off.get()), static_cast<std::int64_t*>(arm.get()),
+                                colored ? static_cast<std::uint64_t*>(arm_rows.get()) : nullptr, &n_bubbles, &n_arm));
+    out.ends = ends.ToHost<std::int64_t>(2 * nb);
+    out.arm_offsets = arm_off.ToHost<std::int64_t>(2 * nb + 1);
+    out.arm_strings = arm.ToHost<std::int64_t>(na);
+    if (colored) out.arm_rows = arm_rows.ToHost<std::uint64_t>(4 * nb);
+    return out;
+  }
+
   // bucket_ids[i] = j  <->  result[i] holds the sorted keys of bucket j.
   std::vector<std::vector<KeyType>> GetSampledKmerSet(const std::vector<int>& bucket_ids, bool canonical,
                                                       int n_workers) const {

@@ -534,6 +534,26 @@ class KmerSetSetIndex {
     return out;
   }
 
+  // The bubbles of that graph (KmerSetCompact::LinkBubbles of its links, ksh_link_bubbles) with the graph's classes
+  // passed in: `graph` is ColoredGraph(cols), `bubbles` its variant sites with arms of at most max_arm strings, and
+  // bit a of an arm's two words in bubbles.arm_rows is column cols[a].  The graph is built canonical: the call takes
+  // no other links.
+  struct ColoredBubblesResult {
+    ColoredGraphResult graph;
+    typename KmerSetCompact<K, N, KeyType>::BubbleList bubbles;
+  };
+  ColoredBubblesResult ColoredBubbles(const std::vector<int>& cols, int max_arm = 8) const {
+    ColoredBubblesResult out;
+    out.graph = ColoredGraph(cols, true);
+    std::vector<std::uint64_t> rows;
+    rows.reserve(2 * out.graph.classes.size());
+    for (const ColorClass& c : out.graph.classes) rows.insert(rows.end(), {c.row[0], c.row[1]});
+    if (out.graph.cls.empty()) rows.clear();  // (no string, no class to name: the call takes no empty table)
+    out.bubbles = KmerSetCompact<K, N, KeyType>::LinkBubbles(out.graph.links.offsets, out.graph.links.to, max_arm,
+                                                            out.graph.cls, rows);
+    return out;
+  }
+
  private:
   static ksh_kss_selection Selection(const std::vector<std::int32_t>& ids, int min_count, int max_count,
                                      const std::vector<std::int32_t>& req, const std::vector<std::int32_t>& exc) {

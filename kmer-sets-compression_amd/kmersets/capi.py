@@ -66,6 +66,13 @@ class Selection(C.Structure):
                 ("n_require", C.c_int32), ("exclude", C.POINTER(C.c_int32)), ("n_exclude", C.c_int32)]
 
 
+class LinkGraph(C.Structure):
+    """ksh_link_graph; the link arrays and the classes are device pointers, rows is a host array."""
+    _fields_ = [("struct_size", C.c_size_t), ("n_strings", C.c_int64), ("d_link_offsets", C.c_void_p),
+                ("d_link_to", C.c_void_p), ("n_links", C.c_int64), ("d_string_class", C.c_void_p),
+                ("rows", C.POINTER(C.c_uint64)), ("n_classes", C.c_int64)]
+
+
 class SeqPaint(C.Structure):
     """ksh_seq_paint; cols and rows are host arrays."""
     _fields_ = [("struct_size", C.c_size_t), ("cols", C.POINTER(C.c_int32)), ("n_cols", C.c_int32),
@@ -210,6 +217,8 @@ def lib():
                                          C.POINTER(i64)]),
         "ksh_spss_cut": (C.c_int, [C.POINTER(SpssView), vp, GP, vp, vp, i64, vp, vp, C.POINTER(i64)]),
         "ksh_spss_links": (C.c_int, [C.POINTER(SpssView), vp, GP, C.c_int, i64, vp, vp, C.POINTER(i64)]),
+        "ksh_link_bubbles": (C.c_int, [C.POINTER(LinkGraph), vp, C.c_int32, i64, i64, vp, vp, vp, vp, C.POINTER(i64),
+                                       C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -275,6 +284,61 @@ def write_gfa(path, strings, k, link_offsets, link_to, string_class=None):
     lines = gfa_lines(strings, k, link_offsets, link_to, string_class)
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
+    return len(lines)
+
+
+def _host_i64(x):
+    return np.asarray(x.cpu() if hasattr(x, "cpu") else x).reshape(-1).astype(np.int64)
+
+
+_COMPLEMENT = str.maketrans("ACGT", "TGCA")
+
+
+def bubble_alleles(strings, k, ends, arm_offsets, arm_strings):
+    """The bubbles of Context.link_bubbles as text over the downloaded strings: one (v, w, allele_0, allele_1) per
+    bubble.  An allele is its arm spelled: the oriented strings of the arm (2 s string s as written, 2 s + 1 its
+    reverse complement) joined on their K - 1 overlaps, so it carries the K - 1 bases of the source's end in front
+    and the K - 1 bases of the sink's start behind.  ends, arm_offsets, arm_strings: tensors, arrays or lists."""
+    ends, off, arm = _host_i64(ends).reshape(-1, 2), _host_i64(arm_offsets), _host_i64(arm_strings)
+    if off.size != 2 * len(ends) + 1:
+        raise ValueError("bubble_alleles: %d bubbles need %d arm offsets" % (len(ends), 2 * len(ends) + 1))
+    k = int(k)
+
+    def spell(a):
+        text = ""
+        for x in arm[off[a]:off[a + 1]]:
+            t = strings[int(x) >> 1]
+            t = t.translate(_COMPLEMENT)[::-1] if int(x) & 1 else t
+            text = t if not text else text + t[k - 1:]
+        return text
+
+    return [(int(v), int(w), spell(2 * b), spell(2 * b + 1)) for b, (v, w) in enumerate(ends)]
+
+
+def bubble_lines(strings, k, ends, arm_offsets, arm_strings, arm_rows=None, n_cols=None):
+    """One tab-separated line per bubble, without newlines: source, sink, allele_0, allele_1, the carriers of arm 0,
+    the carriers of arm 1.  Source and sink are oriented strings; the alleles are bubble_alleles; the carriers of an
+    arm are the comma-separated column positions whose bit is set in its row of arm_rows (uint64[2 nb, 2]; below
+    n_cols if given), '.' for none -- also without arm_rows."""
+    rows = None
+    if arm_rows is not None:
+        rows = np.asarray(arm_rows.cpu() if hasattr(arm_rows, "cpu") else arm_rows).reshape(-1, 2).astype(np.uint64)
+    lines = []
+    for b, (v, w, a0, a1) in enumerate(bubble_alleles(strings, k, ends, arm_offsets, arm_strings)):
+        carriers = []
+        for a in (2 * b, 2 * b + 1):
+            bits = 0 if rows is None else int(rows[a, 0]) | int(rows[a, 1]) << 64
+            cols = [str(c) for c in range(128 if n_cols is None else int(n_cols)) if bits >> c & 1]
+            carriers.append(",".join(cols) if cols else ".")
+        lines.append("%d\t%d\t%s\t%s\t%s\t%s" % (v, w, a0, a1, carriers[0], carriers[1]))
+    return lines
+
+
+def write_bubbles(path, strings, k, ends, arm_offsets, arm_strings, arm_rows=None, n_cols=None):
+    """bubble_lines written to `path`, a newline behind every line.  Returns the number of lines."""
+    lines = bubble_lines(strings, k, ends, arm_offsets, arm_strings, arm_rows, n_cols)
+    with open(path, "w") as f:
+        f.write("".join(line + "\n" for line in lines))
     return len(lines)
 
 
@@ -769,6 +833,60 @@ class Context:
             check(rc)
             assert again == n_links
         return off, link_to[:n_links]
+
+    def link_bubbles_raw(self, link_offsets, link_to, max_arm, capacity, arm_capacity, ends=None, arm_offsets=None,
+                         arm_strings=None, arm_rows=None, string_class=None, rows=None, n_strings=None, n_links=None):
+        """ksh_link_bubbles, one call: (rc, n_bubbles, n_arm_strings).  link_offsets, link_to, string_class and the
+        four outputs: device tensors or None; rows: a host class table or None.  n_strings, n_links: what the graph
+        claims, by default what the tensors hold.  rc is KSH_OK or KSH_FAILED_PRECONDITION (too small a capacity: the
+        message is ksh_last_error); anything else is raised."""
+        import torch
+
+        with torch.cuda.stream(self.stream):
+            table = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+            n = (link_offsets.numel() - 1) // 2 if n_strings is None else int(n_strings)
+            links = (0 if link_to is None else link_to.numel()) if n_links is None else int(n_links)
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            graph = LinkGraph(C.sizeof(LinkGraph), n, ptr(link_offsets), ptr(link_to), links, ptr(string_class),
+                              None if table is None else table.ctypes.data_as(C.POINTER(C.c_uint64)),
+                              0 if table is None else table.size // 2)
+            nb, na = C.c_int64(-1), C.c_int64(-1)
+            rc = lib().ksh_link_bubbles(C.byref(graph), self.h, int(max_arm), int(capacity), int(arm_capacity),
+                                        ptr(ends), ptr(arm_offsets), ptr(arm_strings), ptr(arm_rows), C.byref(nb),
+                                        C.byref(na))
+            del table
+            if rc not in (KSH_OK, KSH_FAILED_PRECONDITION):
+                check(rc)
+            return rc, nb.value, na.value
+
+    def link_bubbles(self, link_offsets, link_to, max_arm=8, string_class=None, rows=None):
+        """ksh_link_bubbles: the bubbles of the link graph that spss_links returns in canonical mode (device int64
+        tensors [2 n + 1] and [n_links]).  A bubble is a source v with two links, two arms of at most max_arm strings
+        each -- every arm string has one link in and one out -- and the sink w where both arms end; it is reported
+        once, as the twin with v <= w ^ 1, ascending by v.  Returns (ends int64[nb, 2], arm_offsets int64[2 nb + 1],
+        arm_strings int64[...], arm_rows uint64[2 nb, 2] or None), device tensors: arm i of bubble b is
+        arm_strings[arm_offsets[2 b + i]:arm_offsets[2 b + i + 1]], oriented strings in walk order, arm 0 the arm of
+        the lower base.  With string_class (device int32[n]) and rows (a class table as color_classes returns it)
+        arm_rows holds the carriers of every arm: the AND of the rows of its strings' classes, the sets that hold
+        every k-mer of the allele; a set that holds only part of an arm is not a carrier.  One call counts, a second
+        one fills."""
+        import torch
+
+        kw = dict(string_class=string_class, rows=rows)
+        rc, nb, na = self.link_bubbles_raw(link_offsets, link_to, max_arm, 0, 0, **kw)
+        check(rc)
+        with torch.cuda.stream(self.stream):
+            ends = torch.empty(2 * max(nb, 1), dtype=torch.int64, device=self.device)
+            arm_off = torch.zeros(2 * max(nb, 1) + 1, dtype=torch.int64, device=self.device)
+            arm = torch.empty(max(na, 1), dtype=torch.int64, device=self.device)
+            arm_rows = None if rows is None else torch.empty(4 * max(nb, 1), dtype=torch.uint64, device=self.device)
+        if nb:
+            rc, again, again_arm = self.link_bubbles_raw(link_offsets, link_to, max_arm, nb, na, ends, arm_off, arm,
+                                                         arm_rows, **kw)
+            check(rc)
+            assert (again, again_arm) == (nb, na)
+        return (ends[:2 * nb].reshape(nb, 2), arm_off[:2 * nb + 1], arm[:na],
+                None if arm_rows is None else arm_rows[:4 * nb].reshape(2 * nb, 2))
 
     def spss_encode_stats(self):
         st = (C.c_int64 * 4)()
@@ -1485,6 +1603,23 @@ class KssIndex:
         spss, cls, rows, counts = self.colored_unitigs(cols, mode=1, route=route, pass_positions=pass_positions)
         off, link_to = self.ctx.spss_links(spss, canonical=self.canonical)
         return spss, cls, rows, counts, off, link_to
+
+    def colored_bubbles(self, cols=None, max_arm=8, route=0, pass_positions=0):
+        """The bubbles of the coloured graph of the columns: the six values of colored_graph(cols, route,
+        pass_positions) followed by the four of Context.link_bubbles on its links with the graph's classes and rows:
+        (spss, string_class, rows, counts, link_offsets, link_to, ends, arm_offsets, arm_strings, arm_rows).  Bit a
+        of an arm's row is column cols[a].  The links are taken as canonical ones: an index built without the
+        canonical flag is refused as soon as its graph has a link."""
+        spss, cls, rows, counts, off, link_to = self.colored_graph(cols, route=route, pass_positions=pass_positions)
+        if spss.n_strings == 0:  # (no string, no class to name: the call takes no empty table)
+            import torch
+
+            bubbles = self.ctx.link_bubbles(off, link_to, max_arm)[:3]
+            with torch.cuda.stream(self.ctx.stream):
+                bubbles += (torch.empty((0, 2), dtype=torch.uint64, device=self.ctx.device),)
+        else:
+            bubbles = self.ctx.link_bubbles(off, link_to, max_arm, string_class=cls, rows=rows)
+        return (spss, cls, rows, counts, off, link_to) + bubbles
 
     @staticmethod
     def class_matrix(rows, n_cols):
