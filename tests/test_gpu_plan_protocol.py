@@ -7,6 +7,13 @@ the truth from a fresh plan + write on the same context.  In both, what the intr
 victim's write.  The truth never comes from the library: numpy set operations with synth.to_bucketed, the oracle's
 strings, geometry_families.kmers_of_strings, np.unique, Python string joins and splits.  Bit-exact throughout.
 
+The columns include the ten calls that take their request first and an index or the context behind it (sequence
+hits, pair counts, selections, colour classes, class ids, class runs, cut, links, bubbles), on the index that borrows
+a built structure and on the one that owns its sets, with their failing variants; their truth is
+tests/index_reference.py, tests/paint_reference.py and the references of the cut, the links and the bubbles.
+test_two_call_requests_keep_no_state shows beside the table that the count / fill forms of those calls keep nothing
+in the library between the two calls.
+
 One context serves a victim row (accumulated state is the point); once any call returns KSH_INTERNAL or a HIP
 error shows, every remaining cell fails without touching the GPU."""
 import ctypes as C
@@ -16,8 +23,11 @@ import numpy as np
 import pytest
 
 import geometry_families as gf
+import link_bubbles_reference as bubbles_ref
 import oracle_lib as ol
 import plan_protocol_cases as cases
+import spss_cut_reference as cut_ref
+import spss_links_reference as links_ref
 from kmersets import capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +131,56 @@ class Data:
         torch.cuda.synchronize()
 
 
+def upload(a, device, dtype=None):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).copy()).to(device)
+
+
+class IndexData:
+    """The host truth of the index ops at one geometry (cases.index_case) and their device inputs: the sequences, and
+    the bucket offsets of both requests as the reference gives them."""
+
+    def __init__(self, geom, device):
+        import torch
+
+        k, n, kb = geom
+        self.geom, self.k, self.g, self.h = geom, k, capi.geom(k, n, kb), cases.index_case(geom)
+        self.dseqs = capi.DeviceSpss.from_strings(self.g, self.h["strings"], device)
+        self.select_off = {name: upload(self.h["select"][name][1], device) for name in "AB"}
+        self.ids_off = {name: upload(self.h["class_ids"][name][2], device) for name in "AB"}
+        torch.cuda.synchronize()
+
+
+class StringData:
+    """The containers, run lists and graphs of the cut, links and bubbles ops at one geometry, their malformed
+    variants, and the references' answers."""
+
+    def __init__(self, geom, device):
+        import torch
+
+        k, n, kb = geom
+        self.geom, self.k, self.g = geom, k, capi.geom(k, n, kb)
+        c = cases.cut_case(k)
+        self.cut = {"seqs": capi.DeviceSpss.from_strings(self.g, c["strings"], device),
+                    "off": upload(c["offsets"], device), "start": upload(c["start"], device),
+                    "bad_off": upload(cases.descending_offsets(c), device),
+                    "want": cut_ref.cut(c["strings"], k, c["offsets"], c["start"])}
+        self.cut["words"] = synth.pack_strings(self.cut["want"][0], k)[0]
+        self.links = {}
+        for which in "AB":
+            strings = cases.links_case(k, which)
+            self.links[which] = {"seqs": capi.DeviceSpss.from_strings(self.g, strings, device),
+                                 "want": links_ref.links(strings, k, True)}
+        self.repeated_end = capi.DeviceSpss.from_strings(self.g, cases.repeated_end(k), device)
+        off, to, max_arm, cls, rows = cases.bubbles_case(kb)
+        self.graph = {"off": upload(off, device), "to": upload(to, device), "bad_to": upload(cases.no_twin(kb), device),
+                      "cls": upload(cls, device, np.int32), "rows": rows,
+                      "max_arm": {"A": max_arm, "B": cases.BUBBLES_MAX_ARM_B}}
+        self.bubbles = {w: bubbles_ref.bubbles(off, to, m, cls, rows) for w, m in self.graph["max_arm"].items()}
+        torch.cuda.synchronize()
+
+
 class Store:
     """Everything that is computed once per module."""
 
@@ -138,14 +198,23 @@ class Store:
         if geom not in self.kss:
             k, n, kb = geom
             g = capi.geom(k, n, kb)
-            sets = [np.asarray(s, dtype=U) for s in synth.phylogeny_sets(k, 4, 3000, seed=77 + k)]
-            strings = [ol.Set.from_kmers(k, *gf.ref_geom(k), s).spss() for s in sets]
+            sets, strings = cases.kss_sets(k), cases.kss_strings(k)
             comps = [capi.DeviceSpss.from_strings(g, st, self.device) for st in strings]
             rng = np.random.default_rng(k)
             q = np.concatenate([rng.choice(s, size=200, replace=False) for s in sets] +
                                [rng.integers(0, 1 << (2 * k), size=200, dtype=np.uint64)]).astype(U)
             self.kss[geom] = {"sets": sets, "comps": comps, "ids": synth.sample_bucket_ids(n, seed=5), "q": q}
         return self.kss[geom]
+
+    def index_data(self, geom):
+        if ("index", geom) not in self.extra:
+            self.extra[("index", geom)] = IndexData(geom, self.device)
+        return self.extra[("index", geom)]
+
+    def string_data(self, geom):
+        if ("strings", geom) not in self.extra:
+            self.extra[("strings", geom)] = StringData(geom, self.device)
+        return self.extra[("strings", geom)]
 
     def large(self):
         """~2 * 10^6 k-mers: a pair of sets and strings with as many k-mers, at (23, 14, u32)."""
@@ -394,10 +463,375 @@ def svb_size(v):
     return (v.size + 3) // 4 + int(lens.sum())
 
 
+# ---- the calls that take their request first ------------------------------------------------------------------------
+# Five of them are issued twice by their callers: count(which) is the counting call of request A or B and returns what
+# the caller holds between the two calls; fill(which, held) is the filling call into sentinel buffers and returns the
+# check of what it wrote; refused(held) is the fill of request A handed what belongs to request B.
+REQUEST = {"A": cases.REQUEST_A, "B": cases.REQUEST_B}
+
+
+def key_part(buf, n_keys, g):
+    """(the first n_keys keys of a sentinel buffer in the key type, whether every byte behind them is intact)"""
+    raw = buf.cpu().numpy()
+    cut = n_keys * g.key_bytes
+    return raw[:cut].view(capi.KEY_DTYPE[g.key_bytes]), bool((raw[cut:] == SENTINEL).all())
+
+
+def part(buf, n, dtype):
+    """(the first n elements of a sentinel buffer, whether every byte behind them is intact)"""
+    import torch
+
+    raw = buf.view(torch.uint8).cpu().numpy()
+    cut = n * np.dtype(dtype).itemsize
+    return raw[:cut].view(dtype), bool((raw[cut:] == SENTINEL).all())
+
+
+def typed(n, dtype, device):
+    """A sentinel buffer of n elements (and TAIL bytes behind them) as a tensor of dtype."""
+    import torch
+
+    size = torch.empty(0, dtype=dtype).element_size()
+    return sentinel(n * size, device)[: n * size + TAIL - TAIL % size].view(dtype)
+
+
+def failed_precondition(fn):
+    with pytest.raises(capi.KshError) as e:
+        fn()
+    stop_on_internal(e.value)
+    assert e.value.code == capi.KSH_FAILED_PRECONDITION, str(e.value)
+    return str(e.value)
+
+
+class SelectCall:
+    """ksh_kss_select_count, then ksh_kss_select_keys."""
+
+    def __init__(self, idx, data):
+        self.idx, self.d, self.dev = idx, data, idx.ctx.device
+
+    def count(self, which):
+        off, n, spec = self.idx.select_count(spectrum=True, **REQUEST[which])
+        kmers, want_off, _ = self.d.h["select"][which]
+        assert n == kmers.size and np.array_equal(off.cpu().numpy(), want_off)
+        assert np.array_equal(spec, self.d.h["spectrum"][which])
+        return off, n
+
+    def fill(self, which, held):
+        off, n = held
+        keys = sentinel(n * self.d.g.key_bytes, self.dev)
+        self.idx.select_write(off, n, keys, **REQUEST[which])
+
+        def verify():
+            got, intact = key_part(keys, n, self.d.g)
+            assert np.array_equal(got, self.d.h["select"][which][2]) and intact, "select %s" % which
+        return verify
+
+    def refused(self, held_a, held_b):
+        """A's fill with B's offsets, then with B's count: refused, nothing at or behind the capacity it was given
+        (the buffer has room for every k-mer of the structure, so even a wrong kernel stays inside it)."""
+        for off, n in ((held_b[0], held_a[1]), (held_a[0], held_b[1])):
+            keys = sentinel(self.d.h["n_distinct"] * self.d.g.key_bytes, self.dev)
+            assert "ksh_kss_select_keys" in failed_precondition(
+                lambda: self.idx.select_write(off, n, keys, **REQUEST["A"]))
+            assert key_part(keys, n, self.d.g)[1], "a refused ksh_kss_select_keys wrote behind its capacity"
+
+
+class ClassIdsCall:
+    """ksh_kss_select_count of the union of the request's columns, then ksh_kss_select_class_ids with the table of
+    those columns."""
+
+    def __init__(self, idx, data):
+        self.idx, self.d, self.dev = idx, data, idx.ctx.device
+
+    def count(self, which):
+        off, n, _ = self.idx.select_count(cols=REQUEST[which]["cols"])
+        _, kmers, want_off, _, _ = self.d.h["class_ids"][which]
+        assert n == kmers.size and np.array_equal(off.cpu().numpy(), want_off)
+        return off, n
+
+    def fill(self, which, held):
+        import torch
+
+        off, n = held
+        rows, _, _, want_keys, want_ids = self.d.h["class_ids"][which]
+        keys, ids = sentinel(n * self.d.g.key_bytes, self.dev), typed(n, torch.int32, self.dev)
+        assert self.idx.select_class_ids(off, n, rows, keys, ids, cols=REQUEST[which]["cols"]) is None
+
+        def verify():
+            got, intact = key_part(keys, n, self.d.g)
+            assert np.array_equal(got, want_keys) and intact, "class ids %s: keys" % which
+            got, intact = part(ids, n, np.int32)
+            assert np.array_equal(got, want_ids) and intact, "class ids %s: ids" % which
+        return verify
+
+    def refused(self, held_a, held_b):
+        import torch
+
+        rows, cols = self.d.h["class_ids"]["A"][0], REQUEST["A"]["cols"]
+        for off, n in ((held_b[0], held_a[1]), (held_a[0], held_b[1])):
+            room = self.d.h["n_distinct"]
+            keys, ids = sentinel(room * self.d.g.key_bytes, self.dev), typed(room, torch.int32, self.dev)
+            assert "ksh_kss_select_class_ids" in failed_precondition(
+                lambda: self.idx.select_class_ids(off, n, rows, keys, ids, cols=cols))
+            assert key_part(keys, n, self.d.g)[1] and part(ids, n, np.int32)[1], \
+                "a refused ksh_kss_select_class_ids wrote behind its capacity"
+
+
+class ClassRunsCall:
+    """ksh_seq_class_runs with capacity 0, then with the number of runs it returned."""
+
+    def __init__(self, idx, data, route=1):
+        self.idx, self.d, self.dev, self.route = idx, data, idx.ctx.device, route
+
+    def raw(self, which, capacity, off, start, cls):
+        table = self.d.h["runs"][which][0]
+        rc, n_runs, missing = self.idx.class_runs_raw(self.d.dseqs, table, capacity, off, start, cls,
+                                                      cols=REQUEST[which]["cols"], canonicalize=True, route=self.route)
+        if rc != capi.KSH_OK:
+            raise capi.KshError(rc, capi.lib().ksh_last_error().decode())
+        return n_runs, missing
+
+    def count(self, which):
+        n_runs, missing = self.raw(which, 0, None, None, None)
+        assert n_runs == int(self.d.h["runs"][which][1][-1]) and missing == 0
+        return n_runs
+
+    def buffers(self, capacity):
+        import torch
+
+        return (typed(self.d.dseqs.n_strings + 1, torch.int64, self.dev), typed(capacity, torch.int32, self.dev),
+                typed(capacity, torch.int32, self.dev))
+
+    def fill(self, which, capacity):
+        off, start, cls = self.buffers(capacity)
+        assert self.raw(which, capacity, off, start, cls) == (capacity, 0)
+
+        def verify():
+            _, want_off, want_start, want_cls, _ = self.d.h["runs"][which]
+            for buf, want, dtype in ((off, want_off, np.int64), (start, want_start, np.int32), (cls, want_cls, np.int32)):
+                got, intact = part(buf, want.size, dtype)
+                assert np.array_equal(got, want) and intact, "class runs %s" % which
+        return verify
+
+    def refused(self, capacity_a, capacity_b):
+        """A's fill with room for B's runs: refused with the true number, nothing at or behind the capacity."""
+        off, start, cls = self.buffers(capacity_b)
+        message = failed_precondition(lambda: self.raw("A", capacity_b, off, start, cls))
+        assert "capacity" in message and str(capacity_a) in message, message
+        assert part(start, capacity_b, np.int32)[1] and part(cls, capacity_b, np.int32)[1]
+        assert part(off, self.d.dseqs.n_strings + 1, np.int64)[1]
+
+
+class LinksCall:
+    """ksh_spss_links with capacity 0, then with the number of links it returned."""
+
+    def __init__(self, ctx, data):
+        self.ctx, self.d, self.dev = ctx, data, ctx.device
+
+    def raw(self, which, capacity, off, to, seqs=None):
+        seqs = seqs or self.d.links[which]["seqs"]
+        rc, n_links = self.ctx.spss_links_raw(seqs, True, capacity, off, to)
+        if rc != capi.KSH_OK:
+            raise capi.KshError(rc, capi.lib().ksh_last_error().decode())
+        return n_links
+
+    def count(self, which):
+        n_links = self.raw(which, 0, None, None)
+        assert n_links == self.d.links[which]["want"][1].size
+        return n_links
+
+    def buffers(self, which, capacity):
+        import torch
+
+        return (typed(2 * self.d.links[which]["seqs"].n_strings + 1, torch.int64, self.dev),
+                typed(capacity, torch.int64, self.dev))
+
+    def fill(self, which, capacity):
+        off, to = self.buffers(which, capacity)
+        assert self.raw(which, capacity, off, to) == capacity
+
+        def verify():
+            for buf, want in zip((off, to), self.d.links[which]["want"]):
+                got, intact = part(buf, want.size, np.int64)
+                assert np.array_equal(got, want) and intact, "links %s" % which
+        return verify
+
+    def refused(self, capacity_a, capacity_b):
+        """A's fill with too small a capacity: refused with the true number, the targets untouched, the offsets
+        (the header: written whenever given) whole."""
+        off, to = self.buffers("A", capacity_b)
+        message = failed_precondition(lambda: self.raw("A", capacity_b, off, to))
+        assert "capacity = %d" % capacity_b in message and "n_links = %d" % capacity_a in message, message
+        assert all_sentinel(to), "a refused ksh_spss_links touched d_link_to"
+        want = self.d.links["A"]["want"][0]
+        got, intact = part(off, want.size, np.int64)
+        assert np.array_equal(got, want) and intact
+
+
+class BubblesCall:
+    """ksh_link_bubbles with both capacities 0, then with the two numbers it returned."""
+
+    def __init__(self, ctx, data):
+        self.ctx, self.d, self.dev = ctx, data, ctx.device
+
+    def raw(self, which, nb, na, bufs, to=None):
+        g = self.d.graph
+        rc, got_nb, got_na = self.ctx.link_bubbles_raw(g["off"], g["to"] if to is None else to, g["max_arm"][which], nb,
+                                                       na, *bufs, string_class=g["cls"], rows=g["rows"])
+        if rc != capi.KSH_OK:
+            raise capi.KshError(rc, capi.lib().ksh_last_error().decode())
+        return got_nb, got_na
+
+    def count(self, which):
+        held = self.raw(which, 0, 0, (None, None, None, None))
+        want = self.d.bubbles[which]
+        assert held == (len(want[0]), len(want[2]))
+        return held
+
+    def buffers(self, nb, na):
+        import torch
+
+        return [typed(size, torch.int64, self.dev) for size in (2 * nb, 2 * nb + 1, na, 4 * nb)]
+
+    def fill(self, which, held):
+        nb, na = held
+        bufs = self.buffers(nb, na)
+        assert self.raw(which, nb, na, bufs) == held
+
+        def verify():
+            ends, arm_off, arm, arm_rows = self.d.bubbles[which]
+            wants = (ends.reshape(-1), arm_off, arm, arm_rows.reshape(-1).view(np.int64))
+            for buf, want in zip(bufs, wants):
+                got, intact = part(buf, want.size, np.int64)
+                assert np.array_equal(got, want) and intact, "bubbles %s" % which
+        return verify
+
+    def refused(self, held_a, held_b):
+        """A's fill with B's capacities: refused with the true numbers, all four outputs untouched."""
+        bufs = self.buffers(*held_b)
+        message = failed_precondition(lambda: self.raw("A", held_b[0], held_b[1], bufs))
+        assert "capacity = %d but n_bubbles = %d" % (held_b[0], held_a[0]) in message, message
+        assert all(all_sentinel(b) for b in bufs), "a refused ksh_link_bubbles touched an output"
+
+
+def raw_cut(ctx, seqs, off, start, n_runs, words, lens):
+    """ksh_spss_cut itself -> (status, n_bases_out)."""
+    import torch
+
+    view, n = seqs.view(), C.c_int64(-7)
+    with torch.cuda.stream(ctx.stream):
+        rc = capi.lib().ksh_spss_cut(C.byref(view), ctx.h, C.byref(seqs.g), off.data_ptr(), start.data_ptr(), n_runs,
+                                     words.data_ptr(), lens.data_ptr(), C.byref(n))
+    if rc == capi.KSH_INTERNAL:
+        capi.check(rc)
+    return rc, n.value
+
+
+def run_cut(ctx, data, bad=False):
+    import torch
+
+    c = data.cut
+    strings, want_lens, n_out = c["want"]
+    n_words, n_runs = (n_out + 31) // 32, len(strings)
+    words, lens = typed(n_words, torch.int64, ctx.device), typed(n_runs, torch.int32, ctx.device)
+    rc, n = raw_cut(ctx, c["seqs"], c["bad_off"] if bad else c["off"], c["start"], n_runs, words, lens)
+    if bad:
+        message = capi.lib().ksh_last_error().decode()
+        assert rc == capi.KSH_INVALID_ARGUMENT and "string 3 has no run" in message, (rc, message)
+        assert all_sentinel(words) and all_sentinel(lens), "a refused ksh_spss_cut touched an output"
+        return lambda: None
+    assert (rc, n) == (capi.KSH_OK, n_out), capi.lib().ksh_last_error().decode()
+
+    def verify():
+        got, intact = part(words, n_words, np.uint64)
+        got = got.copy()
+        if n_out % 32:  # (the bits behind the last base are unspecified)
+            got[-1] &= ~U(0) << U(64 - 2 * (n_out % 32))
+        assert np.array_equal(got, c["words"]) and intact, "cut: words"
+        got, intact = part(lens, n_runs, np.uint32)
+        assert np.array_equal(got, want_lens) and intact, "cut: lens"
+    return verify
+
+
+def indexes(state, geom):
+    """(the index that borrows the build's sets, the index that owns decoded ones) the row keeps at this geometry."""
+    return state[("borrowed", geom)], state[("owned", geom)]
+
+
+def run_new_op(op, ctx, store, geom, state):
+    """One of the ops over the ten calls that take their request first, and their failing variants."""
+    if op in cases.INDEX_OPS + ["fail:select_keys"]:
+        d = store.index_data(geom)
+        h = d.h
+        checks = []
+        for at, idx in enumerate(indexes(state, geom)):
+            assert idx.ctx is ctx
+            route = 1 + at  # the search on the borrowed index, the join on the owned one
+            if op == "seq_hits":
+                got = idx.seq_hits(d.dseqs, canonicalize=True, route=route)
+                checks.append(lambda got=got: np.array_equal(got[:, :cases.KSS_SETS], h["hits"]) or pytest.fail(op))
+            elif op == "pair_counts":
+                got = idx.pair_counts(cols=cases.COLS, with_distinct=True)
+                checks.append(lambda got=got: (np.array_equal(got[0], h["pairs"]) and got[1] == h["n_distinct"])
+                              or pytest.fail(op))
+            elif op == "select":
+                call = SelectCall(idx, d)
+                checks.append(call.fill("A", call.count("A")))
+            elif op == "classes":
+                got = idx.color_classes(cases.COLS, capacity=1 << len(cases.COLS))
+                checks.append(lambda got=got: (np.array_equal(got[0], h["rows"]) and np.array_equal(got[1], h["counts"]))
+                              or pytest.fail(op))
+            elif op == "class_ids":  # (the offsets are the reference's: the op is this one call)
+                checks.append(ClassIdsCall(idx, d).fill("A", (d.ids_off["A"], h["class_ids"]["A"][1].size)))
+            elif op == "class_runs":
+                checks.append(ClassRunsCall(idx, d, route).fill("A", int(h["runs"]["A"][1][-1])))
+            else:  # fail:select_keys: request A's keys at the offsets of request B
+                n = h["select"]["A"][0].size
+                keys = sentinel(h["n_distinct"] * d.g.key_bytes, ctx.device)
+                failed_precondition(lambda: idx.select_write(d.select_off["B"], n, keys, **cases.REQUEST_A))
+                assert key_part(keys, n, d.g)[1], "a refused ksh_kss_select_keys wrote behind its capacity"
+        return lambda: [check() for check in checks]
+    d = store.string_data(geom)
+    if op == "cut":
+        return run_cut(ctx, d)
+    if op == "fail:cut":
+        return run_cut(ctx, d, bad=True)
+    if op == "links":
+        return LinksCall(ctx, d).fill("A", d.links["A"]["want"][1].size)
+    if op == "bubbles":
+        want = d.bubbles["A"]
+        return BubblesCall(ctx, d).fill("A", (len(want[0]), len(want[2])))
+    if op == "fail:links_capacity":
+        n_links = d.links["A"]["want"][1].size
+        LinksCall(ctx, d).refused(n_links, n_links - 1)
+        return lambda: None
+    if op == "fail:links_end":
+        call = LinksCall(ctx, d)
+        off, to = call.buffers("A", 16)
+        off = typed(2 * d.repeated_end.n_strings + 1, off.dtype, ctx.device)
+        with pytest.raises(capi.KshError) as e:
+            call.raw("A", 16, off, to, seqs=d.repeated_end)
+        stop_on_internal(e.value)
+        assert e.value.code == capi.KSH_INVALID_ARGUMENT and "string 1 " in str(e.value), str(e.value)
+        assert all_sentinel(off) and all_sentinel(to), "a refused ksh_spss_links touched an output"
+        return lambda: None
+    assert op == "fail:bubbles", op
+    call = BubblesCall(ctx, d)
+    want = d.bubbles["A"]
+    bufs = call.buffers(len(want[0]), len(want[2]))
+    with pytest.raises(capi.KshError) as e:
+        call.raw("A", len(want[0]), len(want[2]), bufs, to=d.graph["bad_to"])
+    stop_on_internal(e.value)
+    assert e.value.code == capi.KSH_INVALID_ARGUMENT and "has no twin" in str(e.value), str(e.value)
+    assert all(all_sentinel(b) for b in bufs), "a refused ksh_link_bubbles touched an output"
+    return lambda: None
+
+
 def run_intruder(col, ctx, store, geom, state):
     """Runs one intruder on ctx; returns a function that checks what it produced (called after the victim's write)."""
     op = col["op"]
     L = capi.lib()
+    if op in cases.INDEX_OPS + cases.STRING_OPS + cases.NEW_FAILING:
+        return run_new_op(op, ctx, store, geom, state)
     if op.startswith(("full:", "abandon:", "plain:")):
         how, kind = op.split(":")
         d = store.get(geom, "intruder")
@@ -535,7 +969,7 @@ def run_intruder(col, ctx, store, geom, state):
         ks = store.kss_inputs(geom)
         ctx.set_lanes(1 if op.endswith("lanes1") else 0)
         dk = capi.DeviceKmerSetSet(ctx, ks["comps"], ks["ids"])
-        state["kss"] = dk
+        state[("kss", geom)] = dk
         n_nodes = dk.size()
         st = dk.stats()
         assert st["nodes"] == n_nodes >= 4
@@ -548,24 +982,29 @@ def run_intruder(col, ctx, store, geom, state):
             assert np.array_equal(dk.get_kmers(3), ks["sets"][3])
         return verify
     if op == "kss_get":
-        ks, dk = store.kss_inputs(geom), state["kss"]
+        ks, dk = store.kss_inputs(geom), state[("kss", geom)]
         got = dk.get_kmers(1)
         return lambda: np.array_equal(got, ks["sets"][1]) or pytest.fail("kss_get")
     if op in ("kss_index_query", "kss_index_create"):
         ks = store.kss_inputs(geom)
         q = ks["q"]
         if op == "kss_index_query":
-            idx = capi.KssIndex.from_kss(state["kss"])
+            idx = state[("borrowed", geom)] = capi.KssIndex.from_kss(state[("kss", geom)])
+            assert idx.info()["n_nodes"] == state[("kss", geom)].size()
         else:
-            idx = capi.KssIndex.from_nodes(ctx, ks["comps"], [[] for _ in ks["comps"]])
+            idx = state[("owned", geom)] = capi.KssIndex.from_nodes(ctx, ks["comps"], [[] for _ in ks["comps"]])
             assert idx.info()["n_nodes"] == len(ks["comps"])
         got = idx.query(q, canonicalize=True, route=1)
         assert idx.routes() & capi.QROUTE_SEARCH
-        idx.close()
+        # (the index stays open for the columns behind this one; kss_index_close ends it)
         want = np.stack([np.isin(synth.canonical(q, k).astype(U), s) for s in ks["sets"]], axis=1)
         return lambda: np.array_equal(got[:, : len(ks["sets"])], want) or pytest.fail(op)
+    if op == "kss_index_close":
+        state.pop(("borrowed", geom)).close()
+        state.pop(("owned", geom)).close()
+        return lambda: None
     if op == "kss_destroy":
-        state.pop("kss").close()
+        state.pop(("kss", geom)).close()
         return lambda: None
     if op in ("large:arena", "large:plans"):
         lg = store.large()
@@ -662,6 +1101,7 @@ def test_victim_row(store, row):
             if STOP["why"]:
                 failures.append("%s: not run (stopped: %s)" % (col["id"], STOP["why"]))
                 continue
+            cell_t0 = time.time()
             try:
                 run_cell(row, col, ctxs, store, states)
             except BaseException as e:  # noqa: B902 -- every cell is reported; an internal error stops the module
@@ -669,14 +1109,17 @@ def test_victim_row(store, row):
                 failures.append("%s: %s: %s" % (col["id"], type(e).__name__, str(e)[:300]))
                 if isinstance(e, KeyboardInterrupt):
                     raise
+            spent = WALL.setdefault("ops", {}).setdefault(col["op"], [0.0, 0.0])
+            spent[row["geom"][1] >= 20] += time.time() - cell_t0
     finally:
         if not STOP["why"]:
             import torch
 
             torch.cuda.synchronize()
-            for st in states.values():
-                if "kss" in st:
-                    st.pop("kss").close()
+            for st in states.values():  # the indexes before the structures they borrow from
+                for kind in ("borrowed", "owned", "kss"):
+                    for key in [key for key in st if isinstance(key, tuple) and key[0] == kind]:
+                        st.pop(key).close()
             for c in ctxs.values():
                 c.close()
     WALL["rows"] = WALL.get("rows", 0.0) + time.time() - t0
@@ -874,9 +1317,57 @@ def test_plan_on_one_context_write_on_another(ctx, store):
     use(ctx)
 
 
+def column(op):
+    return next(c for c in cases.INTRUDERS if c["op"] == op and c["where"] == "own" and c["width"] == "same")
+
+
+@pytest.mark.parametrize("geom", cases.NARROW, ids=lambda g: "k%d-N%d-u%d" % (g[0], g[1], 8 * g[2]))
+@stops_module
+def test_two_call_requests_keep_no_state(ctx, store, geom):
+    """Five of the calls that take their request first are issued twice by their callers: a counting call, then a
+    filling call with what the count returned.  The caller holds everything between the two; the library holds
+    nothing.  So: count request A, run an intruder, fill A -- exact against the reference, whatever the intruder was:
+    the same call counting request B on the same index or context (other columns, another container, another
+    max_arm), each op over the ten calls, one victim of each plan group as plan + write.  And a fill that is handed
+    B's offsets or B's count is refused, with every sentinel byte at or behind the capacity it was given intact
+    (all of them where the header says the outputs stay untouched)."""
+    state = {}
+    try:
+        for op in ("kss_build:lanes1", "kss_index_query", "kss_index_create"):
+            run_intruder(column(op), ctx, store, geom, state)()
+        d, sd = store.index_data(geom), store.string_data(geom)
+        borrowed, owned = indexes(state, geom)
+        calls = [SelectCall(borrowed, d), SelectCall(owned, d), ClassIdsCall(borrowed, d), ClassIdsCall(owned, d),
+                 ClassRunsCall(borrowed, d, 1), ClassRunsCall(owned, d, 2), LinksCall(ctx, sd), BubblesCall(ctx, sd)]
+        others = [column(op) for op in cases.INDEX_OPS + cases.STRING_OPS] + \
+                 [column("full:" + kinds[0]) for kinds in cases.GROUPS.values()]
+        assert len(others) == 9 + 4
+        for call in calls:
+            intruders = [lambda: (call.count("B"), lambda: None)[1]] + \
+                        [lambda col=col: run_intruder(col, ctx, store, geom, state) for col in others]
+            for intrude in intruders:
+                held = call.count("A")
+                check_intruder = intrude()
+                call.fill("A", held)()
+                check_intruder()
+            held_a, held_b = call.count("A"), call.count("B")
+            call.refused(held_a, held_b)
+            call.fill("A", held_a)()  # (and the call still serves)
+            call.fill("B", held_b)()
+    finally:
+        if not STOP["why"]:
+            import torch
+
+            torch.cuda.synchronize()
+            for kind in ("borrowed", "owned", "kss"):
+                if (kind, geom) in state:
+                    state.pop((kind, geom)).close()
+
+
 def test_outcome_table():
     """The victim x intruder outcome table (run with -s): one line per victim kind and intruder op, `E` exact,
-    `R` refused, in the order own context same width / other width / second context."""
+    `R` refused, in the order own context same width / other width / second context; behind them the seconds the op's
+    cells took, so that an op that rebuilds something per cell shows."""
     guard()
     if not set(WALL.get("ran", ())) >= {v["id"] for v in cases.VICTIMS}:
         pytest.skip("the table needs every victim row in the same run: select the whole module")
@@ -896,6 +1387,8 @@ def test_outcome_table():
                 got = {OUTCOMES[(v["id"], c["id"])] for v in cases.VICTIMS if v["kind"] == kind}
                 marks += "E" if got == {cases.EXACT} else "R" if got == {cases.REFUSED} else "?"
             cells.append("%-9s" % marks)
-        print("%-20s %s" % (op, " ".join(cells)))
+        narrow, wide = WALL.get("ops", {}).get(op, (0.0, 0.0))
+        print("%-20s %s %6.2f s + %.2f s" % (op, " ".join(cells), narrow, wide))
+    print("(seconds per op over all its cells: the rows below N = 20, and the rows at N = 20)")
     print("replay: " + ", ".join("%s%s %s" % (k, "(plain)" if plain else "", r) for (k, plain), r in REPLAY.items()))
     print("wall: rows %.1f s, module so far %.1f s" % (WALL.get("rows", 0.0), time.time() - T0))

@@ -15,7 +15,7 @@ NAME = "ksh_link_bubbles"
 
 def test_header_declares_the_call_with_the_graph_first():
     decl = protocol.declarations()
-    assert decl.get(NAME) == "const ksh_link_graph* graph"
+    assert decl.get(NAME)[0] == "const ksh_link_graph* graph"
     assert NAME in capi.exported_symbols()
     text = re.sub(r"/\*.*?\*/", "", open(capi.HEADER).read(), flags=re.S)
     params = re.search(r"\bint\s+ksh_link_bubbles\s*\(([^)]*)\)", text).group(1)
@@ -121,9 +121,12 @@ def test_python_wrappers_exist():
 
 
 def test_plan_protocol_table_is_unchanged_and_complete():
-    """The call is no plan, no write and takes no context first: the table needs no row for it, and every check of
-    tests/test_plan_protocol_cpu.py holds as it stands."""
-    assert not any(NAME in c["symbols"] for c in cases.INTRUDERS) and NAME not in cases.EXCLUDED
+    """The call is no plan and no write, so the table has no row for it; it takes a context behind its request, so it
+    is an intruder column on the victim's context and on the second one, it ends no plan, and every check of
+    tests/test_plan_protocol_cpu.py holds."""
+    mine = [c for c in cases.INTRUDERS if NAME in c["symbols"]]
+    assert {c["where"] for c in mine} == {"own", "second"} and NAME not in cases.EXCLUDED
+    assert all(c["refuses"] == () for c in mine) and any(not c["op"].startswith("fail:") for c in mine)
     protocol.test_every_plan_write_pair_is_a_victim()
     protocol.test_every_context_entry_point_is_an_intruder()
     protocol.test_refusals_only_where_the_contract_permits()
