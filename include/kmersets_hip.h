@@ -1014,6 +1014,47 @@ int ksh_link_bubbles(const ksh_link_graph* graph, ksh_ctx* ctx, int32_t max_arm,
                      int64_t arm_capacity, int64_t* d_bubble_ends, int64_t* d_arm_offsets, int64_t* d_arm_strings,
                      uint64_t* d_arm_rows, int64_t* n_bubbles, int64_t* n_arm_strings);
 
+/* ---- Where the string ends of one container occur in another: the graph placed on a reference ----------------------
+ * Two containers: n strings, whose 2 n ends are located, and a reference of m sequences, whose k-mers may repeat.
+ * End e = 2 s is the first k-mer of string s as written, e = 2 s + 1 its last; for a one-k-mer string both ends are
+ * the same k-mer.  Ends need not be distinct, within a string or between strings: unitigs, cut unitigs and reads are
+ * all taken.
+ * The reference's k-mer positions are numbered in one line, as for ksh_seq_hits: sequence r owns the global positions
+ * pstart[r] .. pstart[r + 1), pstart being the exclusive scan of lens + 1, and a window never crosses from one
+ * sequence into the next.  A position with k-mer x matches an end k-mer y when x == y (strand 0) or, with
+ * canonical != 0 only, x == rc(y) (strand 1).  A k-mer that is its own reverse complement (even K) reads strand 0.
+ * d_count[e] is the number of matching positions; d_where[e] is (g << 1) | strand of the matching position with the
+ * smallest global index g, -1 when there is none.  The host turns g into (sequence, position) with pstart.
+ * *n_located (host, may be NULL) is the number of ends with d_count[e] >= 1.
+ * The result is a function of the two containers alone.  Nothing is written outside [0, 2 n) of either output.
+ * n_strings == 0 of `strings`: KSH_OK, *n_located = 0, nothing is written and the device is not touched.  A reference
+ * of no sequences: -1 and 0 everywhere.  A reference of 2^32 k-mer positions or more is refused, so d_count is exact.
+ * KSH_INVALID_ARGUMENT, each with a message that names the field.  On the host: NULL req, ctx, g or strings; a
+ * struct_size smaller than the struct; negative sizes of either view; a geometry no call accepts; K < 4; with strings
+ * a NULL reference, NULL words or lens of a container that has sequences, a NULL d_where or d_count.  On the device,
+ * before any output element is written, naming the container and the first offending string: what ksh_seq_hits
+ * refuses, lens[s] == UINT32_MAX and sum(lens + K) != n_bases, of the strings first and of the reference second (each
+ * before that container's words are read).  The context still serves after any refusal.
+ * The call is stateless like ksh_spss_links: scratch comes from the context's pool (24 bytes per string, 8 bytes per
+ * reference sequence, and 20 bytes per slot of an end table of the next power of two >= 4 n slots) and is given back
+ * before the call returns; it keeps no plan, joins no plan group and ends no pending plan.  It synchronises the
+ * context's stream three times: for the sizes of the strings, for those of the reference, and at the end (twice when
+ * the reference has no sequences).
+ * The request is the only parameter: the context is a field of it. */
+typedef struct ksh_seq_locate_req {
+  size_t struct_size;
+  ksh_ctx* ctx;
+  const ksh_geom* g;
+  const ksh_spss_view* strings;   /* n strings: their 2 n ends are located   */
+  const ksh_spss_view* reference; /* m sequences; k-mers may repeat          */
+  int32_t canonical;
+  int64_t* d_where;               /* device int64[2 n]                       */
+  uint32_t* d_count;              /* device uint32[2 n]                      */
+  int64_t* n_located;             /* host, may be NULL: ends with count >= 1 */
+} ksh_seq_locate_req;
+
+int ksh_seq_locate(const ksh_seq_locate_req* req);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,38 @@ class KmerSetCompact {
     return out;
   }
 
+  // Where the ends of the strings occur in `reference` (ksh_seq_locate).  End 2 s is the first k-mer of string s as
+  // written, end 2 s + 1 its last.  count[e] is the number of k-mer positions of the reference that hold the end's
+  // k-mer (canonical: or its reverse complement); where[e] is (g << 1) | strand of the one with the smallest global
+  // position g, strand 1 meaning that the reference reads the reverse complement, or -1.  Global positions number
+  // the k-mer positions of all reference sequences in one line: sequence r owns length(r) - K + 1 of them.
+  struct LocateList {
+    std::vector<std::int64_t> where;
+    std::vector<std::uint32_t> count;
+    std::int64_t n_located = 0;
+  };
+  LocateList Locate(const KmerSetCompact& reference, bool canonical = true) const {
+    const ksh_geom g = Set::Geom();
+    const ksh_spss_view strings = View(), ref = reference.View();
+    LocateList out;
+    if (n_ == 0) return out;
+    ksc::DeviceBuffer where(std::size_t(2 * n_) * 8), count(std::size_t(2 * n_) * 4);
+    ksh_seq_locate_req req{};
+    req.struct_size = sizeof(req);
+    req.ctx = ksc::Ctx();
+    req.g = &g;
+    req.strings = &strings;
+    req.reference = &ref;
+    req.canonical = canonical ? 1 : 0;
+    req.d_where = static_cast<std::int64_t*>(where.get());
+    req.d_count = static_cast<std::uint32_t*>(count.get());
+    req.n_located = &out.n_located;
+    ksc::Check(ksh_seq_locate(&req));
+    out.where = where.ToHost<std::int64_t>(std::size_t(2 * n_));
+    out.count = count.ToHost<std::uint32_t>(std::size_t(2 * n_));
+    return out;
+  }
+
   // bucket_ids[i] = j  <->  result[i] holds the sorted keys of bucket j.
   std::vector<std::vector<KeyType>> GetSampledKmerSet(const std::vector<int>& bucket_ids, bool canonical,
                                                       int n_workers) const {

@@ -1,5 +1,6 @@
 // What the calls that walk the k-mer positions of sequences share: ksh_seq_hits (ksh_seqhits.hip, which defines
-// everything declared here) and ksh_seq_class_runs (ksh_paint.hip).  DESIGN.md 3.8b, 3.8g.  gfx950 only.
+// everything declared here), ksh_seq_class_runs (ksh_paint.hip) and ksh_seq_locate (ksh_locate.hip).  DESIGN.md 3.8b,
+// 3.8g, 3.8m.  gfx950 only.
 //
 // The positions of all sequences are numbered in one line: sequence s owns positions pstart[s] .. pstart[s + 1)
 // (pstart = exclusive scan of lens + 1), and the k-mer of position p of sequence s starts at base p + s (K - 1).

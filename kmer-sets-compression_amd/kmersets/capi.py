@@ -73,6 +73,13 @@ class LinkGraph(C.Structure):
                 ("rows", C.POINTER(C.c_uint64)), ("n_classes", C.c_int64)]
 
 
+class LocateReq(C.Structure):
+    """ksh_seq_locate_req; the views are host structs of device pointers, the outputs device pointers."""
+    _fields_ = [("struct_size", C.c_size_t), ("ctx", C.c_void_p), ("g", C.POINTER(Geom)),
+                ("strings", C.POINTER(SpssView)), ("reference", C.POINTER(SpssView)), ("canonical", C.c_int32),
+                ("d_where", C.c_void_p), ("d_count", C.c_void_p), ("n_located", C.POINTER(C.c_int64))]
+
+
 class SeqPaint(C.Structure):
     """ksh_seq_paint; cols and rows are host arrays."""
     _fields_ = [("struct_size", C.c_size_t), ("cols", C.POINTER(C.c_int32)), ("n_cols", C.c_int32),
@@ -219,6 +226,7 @@ def lib():
         "ksh_spss_links": (C.c_int, [C.POINTER(SpssView), vp, GP, C.c_int, i64, vp, vp, C.POINTER(i64)]),
         "ksh_link_bubbles": (C.c_int, [C.POINTER(LinkGraph), vp, C.c_int32, i64, i64, vp, vp, vp, vp, C.POINTER(i64),
                                        C.POINTER(i64)]),
+        "ksh_seq_locate": (C.c_int, [C.POINTER(LocateReq)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -340,6 +348,112 @@ def write_bubbles(path, strings, k, ends, arm_offsets, arm_strings, arm_rows=Non
     with open(path, "w") as f:
         f.write("".join(line + "\n" for line in lines))
     return len(lines)
+
+
+UNPLACED_REASONS = ("anchor", "apart", "order", "off")
+
+
+def place_bubbles(strings, k, ends, arm_offsets, arm_strings, where, count, ref_strings, arm_rows=None, n_cols=None):
+    """The bubbles of Context.link_bubbles placed on a reference: one dict per bubble, in the bubbles' order.  where
+    and count are Context.seq_locate of the graph's strings in the reference, ref_strings the reference's sequences as
+    text.  A placed bubble is {"v", "w", "seq", "pos", "ref", "alt", "gt"}: sequence number, 1-based POS, the two
+    trimmed alleles and, with arm_rows, one genotype per column below n_cols ("0" the column carries the REF arm only,
+    "1" the ALT arm only, "0/1" both, "." neither), else None.  An unplaced one is {"v", "w", "unplaced": reason}:
+      anchor  the exit end of v (end v ^ 1) or the entry end of w (end w) occurs in the reference not exactly once;
+      apart   the two anchors lie in different sequences or on different strands;
+      order   the sink's anchor does not lie behind the source's (after taking the twin on strand 1);
+      off     neither allele spells the reference between the anchors.
+    The reference text of the site is bases [p_a + 1, p_b + K - 1) of the sequence, p_a and p_b the positions of the
+    two anchors; the arm that equals it is REF.  Common trailing bases are trimmed first, then common leading ones,
+    each while both alleles are longer than one base; there is no left-alignment beyond the arms."""
+    k = int(k)
+    where, count = _host_i64(where), _host_i64(count)
+    rows = None
+    if arm_rows is not None:
+        rows = np.asarray(arm_rows.cpu() if hasattr(arm_rows, "cpu") else arm_rows).reshape(-1, 2).astype(np.uint64)
+    pstart = np.concatenate([[0], np.cumsum([len(t) - k + 1 for t in ref_strings])]).astype(np.int64)
+    out = []
+    for b, (v, w, a0, a1) in enumerate(bubble_alleles(strings, k, ends, arm_offsets, arm_strings)):
+        entry = {"v": v, "w": w}
+        out.append(entry)
+        ev, ew = v ^ 1, w
+        if count[ev] != 1 or count[ew] != 1:
+            entry["unplaced"] = "anchor"
+            continue
+        g_v, s_v = int(where[ev]) >> 1, (int(where[ev]) & 1) ^ (v & 1)
+        g_w, s_w = int(where[ew]) >> 1, (int(where[ew]) & 1) ^ (w & 1)
+        r = int(np.searchsorted(pstart, g_v, side="right")) - 1
+        if r != int(np.searchsorted(pstart, g_w, side="right")) - 1 or s_v != s_w:
+            entry["unplaced"] = "apart"
+            continue
+        alleles = [a0, a1]
+        if s_v:
+            g_v, g_w = g_w, g_v
+            alleles = [a.translate(_COMPLEMENT)[::-1] for a in alleles]
+        if g_w <= g_v:
+            entry["unplaced"] = "order"
+            continue
+        start, stop = g_v - int(pstart[r]) + 1, g_w - int(pstart[r]) + k - 1
+        site = ref_strings[r][start:stop]
+        if site not in alleles:
+            entry["unplaced"] = "off"
+            continue
+        ref_arm = alleles.index(site)
+        ref, alt = alleles[ref_arm], alleles[1 - ref_arm]
+        while len(ref) > 1 and len(alt) > 1 and ref[-1] == alt[-1]:
+            ref, alt = ref[:-1], alt[:-1]
+        while len(ref) > 1 and len(alt) > 1 and ref[0] == alt[0]:
+            ref, alt, start = ref[1:], alt[1:], start + 1
+        gt = None
+        if rows is not None:
+            bits = [int(rows[2 * b + a, 0]) | int(rows[2 * b + a, 1]) << 64 for a in (ref_arm, 1 - ref_arm)]
+            gt = [(".", "0", "1", "0/1")[(bits[0] >> c & 1) | (bits[1] >> c & 1) << 1]
+                  for c in range(128 if n_cols is None else int(n_cols))]
+        entry.update(seq=r, pos=start + 1, ref=ref, alt=alt, gt=gt)
+    return out
+
+
+def vcf_lines(records, ref_names, ref_lengths, sample_names=None):
+    """VCF 4.2 text of the placed bubbles among `records` (place_bubbles), a list of lines without newlines, and the
+    counts {"placed", "anchor", "apart", "order", "off"}: the header (fileformat, a contig line per reference
+    sequence, the INFO line of BUB, with genotypes the FORMAT line of GT), the column line, and the records sorted
+    by (sequence, POS, REF, ALT) with ID, QUAL and FILTER '.', BUB=<v>,<w> in INFO and, when the records carry
+    genotypes, a GT column per sample (sample_names, by default S0, S1, ...).  Unplaced bubbles are only counted."""
+    counts = dict.fromkeys(("placed",) + UNPLACED_REASONS, 0)
+    placed = []
+    for rec in records:
+        counts[rec.get("unplaced", "placed")] += 1
+        if "unplaced" not in rec:
+            placed.append(rec)
+    with_gt = bool(placed) and all(rec["gt"] is not None for rec in placed)
+    lines = ["##fileformat=VCFv4.2"]
+    lines += ["##contig=<ID=%s,length=%d>" % (name, int(n)) for name, n in zip(ref_names, ref_lengths)]
+    lines.append('##INFO=<ID=BUB,Number=2,Type=Integer,Description="Source and sink of the bubble, oriented strings '
+                 'of the graph">')
+    cols = ["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO"]
+    if with_gt:
+        lines.append('##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">')
+        n_samples = len(placed[0]["gt"])
+        names = list(sample_names) if sample_names is not None else ["S%d" % c for c in range(n_samples)]
+        if len(names) != n_samples:
+            raise ValueError("vcf_lines: %d sample names for %d genotype columns" % (len(names), n_samples))
+        cols += ["FORMAT"] + names
+    lines.append("\t".join(cols))
+    for rec in sorted(placed, key=lambda r: (r["seq"], r["pos"], r["ref"], r["alt"])):
+        fields = [ref_names[rec["seq"]], str(rec["pos"]), ".", rec["ref"], rec["alt"], ".", ".",
+                  "BUB=%d,%d" % (rec["v"], rec["w"])]
+        if with_gt:
+            fields += ["GT"] + list(rec["gt"])
+        lines.append("\t".join(fields))
+    return lines, counts
+
+
+def write_vcf(path, records, ref_names, ref_lengths, sample_names=None):
+    """vcf_lines written to `path`, a newline behind every line.  Returns the counts."""
+    lines, counts = vcf_lines(records, ref_names, ref_lengths, sample_names)
+    with open(path, "w") as f:
+        f.write("".join(line + "\n" for line in lines))
+    return counts
 
 
 class DeviceSet:
@@ -887,6 +1001,44 @@ class Context:
             assert (again, again_arm) == (nb, na)
         return (ends[:2 * nb].reshape(nb, 2), arm_off[:2 * nb + 1], arm[:na],
                 None if arm_rows is None else arm_rows[:4 * nb].reshape(2 * nb, 2))
+
+    def seq_locate_raw(self, strings, reference, canonical, where=None, count=None, g=None, struct_size=None,
+                       want_located=True):
+        """ksh_seq_locate, one call: (rc, n_located).  strings, reference: a DeviceSpss, an SpssView or None; where
+        (int64) and count (uint32 or int32): device tensors or None.  g: the geometry, by default that of `strings`.
+        rc is the return code, whatever it is: the message is ksh_last_error."""
+        import torch
+
+        with torch.cuda.stream(self.stream):
+            view = lambda x: x.view() if isinstance(x, DeviceSpss) else x  # noqa: E731
+            sv, rv = view(strings), view(reference)
+            g = strings.g if g is None else g
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            got = C.c_int64(-1)
+            req = LocateReq(C.sizeof(LocateReq) if struct_size is None else int(struct_size), self.h,
+                            None if g is None else C.pointer(g), None if sv is None else C.pointer(sv),
+                            None if rv is None else C.pointer(rv), int(bool(canonical)), ptr(where), ptr(count),
+                            C.pointer(got) if want_located else None)
+            rc = lib().ksh_seq_locate(C.byref(req))
+            return rc, got.value
+
+    def seq_locate(self, strings, reference, canonical=True):
+        """ksh_seq_locate: where the ends of `strings` occur in `reference` (both a DeviceSpss).  End 2 s is the first
+        k-mer of string s as written, end 2 s + 1 its last.  Returns (where, count), device tensors int64[2 n] and
+        uint32[2 n]: count[e] is the number of k-mer positions of the reference that hold the end's k-mer (with
+        `canonical`, or its reverse complement), where[e] is (g << 1) | strand of the one with the smallest global
+        position g, strand 1 meaning that the reference reads the reverse complement, or -1.  Global positions number
+        the k-mer positions of all reference sequences in one line: sequence r owns len(r) - K + 1 of them, in the
+        container's order (place_bubbles turns them back)."""
+        import torch
+
+        n = strings.n_strings
+        with torch.cuda.stream(self.stream):
+            where = torch.empty(2 * n, dtype=torch.int64, device=self.device)
+            count = torch.empty(2 * n, dtype=torch.uint32, device=self.device)
+        rc, _ = self.seq_locate_raw(strings, reference, canonical, where, count)
+        check(rc)
+        return where, count
 
     def spss_encode_stats(self):
         st = (C.c_int64 * 4)()
@@ -1620,6 +1772,17 @@ class KssIndex:
         else:
             bubbles = self.ctx.link_bubbles(off, link_to, max_arm, string_class=cls, rows=rows)
         return (spss, cls, rows, counts, off, link_to) + bubbles
+
+    def colored_variants(self, reference, cols=None, max_arm=8, route=0, pass_positions=0):
+        """The bubbles of the coloured graph with the graph placed on a reference: the ten values of
+        colored_bubbles(cols, max_arm, route, pass_positions) followed by (where, count) = Context.seq_locate of the
+        graph's strings in `reference` with the index's canonical flag.  reference: a DeviceSpss (for instance from
+        Context.fasta_fragments) or a list of strings over ACGT of at least K bases each.  capi.place_bubbles and
+        capi.write_vcf make records and VCF text of the twelve values."""
+        out = self.colored_bubbles(cols, max_arm=max_arm, route=route, pass_positions=pass_positions)
+        if not isinstance(reference, DeviceSpss):
+            reference = DeviceSpss.from_strings(self.g, list(reference), self.ctx.device)
+        return out + self.ctx.seq_locate(out[0], reference, canonical=self.canonical)
 
     @staticmethod
     def class_matrix(rows, n_cols):
