@@ -52,6 +52,28 @@ int check_geom(const ksh_geom* g) {
 static void pool_trim_locked(ksh_ctx* ctx);
 static void lanes_release_scratch(ksh_ctx* ctx);
 
+int scratch_fill_now(ksh_ctx* ctx, void* p, size_t bytes) {
+  if (!p || bytes == 0) return KSH_OK;
+  KSH_HIP(hipMemsetAsync(p, ctx->scratch_fill, bytes, ctx->stream));
+  KSH_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->scratch_fills++;
+  ctx->scratch_fill_bytes += int64_t(bytes);
+  return KSH_OK;
+}
+
+// KSH_SCRATCH_FILL (decimal or 0x..): the scratch fill of every context made in this process; unset or out of
+// [0, 255]: off
+static int scratch_fill_default() {
+  static const int v = [] {
+    const char* e = getenv("KSH_SCRATCH_FILL");
+    if (!e || !*e) return -1;
+    char* end = nullptr;
+    const long x = strtol(e, &end, 0);
+    return *end == 0 && x >= 0 && x <= 255 ? int(x) : -1;
+  }();
+  return v;
+}
+
 static size_t device_total_bytes() {
   static const size_t total = [] {
     size_t f = 0, t = 0;
@@ -95,7 +117,7 @@ static int device_alloc_impl(ksh_ctx* ctx, size_t bytes, void** out, bool pool_l
     *out = nullptr;
     return fail(KSH_INTERNAL, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
   }
-  return KSH_OK;
+  return scratch_fill(ctx, *out, bytes);
 }
 
 int device_alloc(ksh_ctx* ctx, size_t bytes, void** out) { return device_alloc_impl(ctx, bytes, out, false); }
@@ -117,11 +139,13 @@ void* arena_alloc(ksh_ctx* ctx, size_t bytes) {
   size_t at = (ctx->arena_used + 255) & ~size_t(255);
   if (at + bytes > ctx->arena_bytes) return nullptr;
   ctx->arena_used = at + bytes;
+  if (scratch_fill(ctx, ctx->arena + at, bytes) != KSH_OK) return nullptr;
   return ctx->arena + at;
 }
 
-int slot_reserve(ksh_ctx* ctx, int which, size_t bytes) {
-  if (bytes <= ctx->slot_bytes[which]) return KSH_OK;
+int slot_reserve(ksh_ctx* ctx, int which, size_t bytes, SlotUse use) {
+  if (bytes <= ctx->slot_bytes[which])
+    return use == kSlotBegin ? scratch_fill(ctx, ctx->slot[which], ctx->slot_bytes[which]) : KSH_OK;
   KSH_HIP(hipStreamSynchronize(ctx->stream));
   if (ctx->slot[which]) KSH_HIP(hipFree(ctx->slot[which]));
   ctx->slot[which] = nullptr;
@@ -155,8 +179,9 @@ int pool_alloc(ksh_ctx* ctx, size_t bytes, void** out) {
     ctx->pool_cached_bytes -= it->first;
     ctx->pool_live_bytes += it->first;
     ctx->pool_peak_bytes = std::max(ctx->pool_peak_bytes, ctx->pool_live_bytes);
+    const size_t have = it->first;  // (the block's own size: up to a quarter more than asked for)
     ctx->pool_free_blocks.erase(it);
-    return KSH_OK;
+    return scratch_fill(ctx, *out, have);
   }
   KSH_TRY(device_alloc_impl(ctx, want, out, true));  // (gives the cached blocks back first when memory is short)
   ctx->pool_sizes[*out] = want;
@@ -277,6 +302,7 @@ int run_on_lanes(ksh_ctx* ctx, const std::vector<size_t>& order, size_t need_byt
       if (ksh_ctx_create(ctx->device, masked, &lane) != KSH_OK) break;  // (no stream, no pinned page: go on with fewer)
       if (masked) lane->own_stream = true;
       lane->lane_parent = ctx;
+      lane->scratch_fill = ctx->scratch_fill;
       ctx->lanes.push_back(lane);
     }
     ksh_ctx* lane = ctx->lanes[l - 1];
@@ -346,7 +372,7 @@ hipEvent_t timer_event(ksh_ctx* ctx, size_t* index) {
 }
 
 int plan_reserve(ksh_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->plan_bytes) return KSH_OK;
+  if (bytes <= ctx->plan_bytes) return scratch_fill(ctx, ctx->plan, ctx->plan_bytes);
   KSH_HIP(hipStreamSynchronize(ctx->stream));
   if (ctx->plan) KSH_HIP(hipFree(ctx->plan));
   ctx->plan = nullptr;
@@ -761,6 +787,7 @@ int ksh_ctx_create(int device, void* stream, ksh_ctx** out) {
   KSH_HIP(hipSetDevice(device));
   ksh_ctx* ctx = new ksh_ctx;
   ctx->device = device;
+  ctx->scratch_fill = scratch_fill_default();
   if (stream) {
     ctx->stream = static_cast<hipStream_t>(stream);
   } else {
@@ -858,6 +885,40 @@ int ksh_ctx_set_lanes(ksh_ctx* ctx, int n_lanes) {
   if (!ctx) return fail(KSH_INVALID_ARGUMENT, "ctx is NULL");
   if (n_lanes > 8) return fail(KSH_INVALID_ARGUMENT, "at most 8 lanes");
   ctx->lanes_wanted = n_lanes < 1 ? -1 : n_lanes;
+  return KSH_OK;
+}
+
+// Test hooks (not in the public header, as ksh_debug_set_tile_trace): the scratch fill and the chained scan's epoch.
+int ksh_debug_set_scratch_fill(ksh_ctx* ctx, int byte) {
+  if (!ctx) return fail(KSH_INVALID_ARGUMENT, "ctx is NULL");
+  if (byte < -1 || byte > 255) return fail(KSH_INVALID_ARGUMENT, "the fill is a byte, or -1 for none");
+  std::vector<ksh_ctx*> all{ctx};
+  all.insert(all.end(), ctx->lanes.begin(), ctx->lanes.end());
+  for (ksh_ctx* c : all) {
+    c->scratch_fill = byte;
+    c->scratch_fills = 0;
+    c->scratch_fill_bytes = 0;
+  }
+  return KSH_OK;
+}
+
+int ksh_debug_scratch_fill_stats(ksh_ctx* ctx, int64_t stats[2]) {
+  if (!ctx || !stats) return fail(KSH_INVALID_ARGUMENT, "NULL argument");
+  stats[0] = ctx->scratch_fills;
+  stats[1] = ctx->scratch_fill_bytes;
+  for (const ksh_ctx* lane : ctx->lanes) {
+    stats[0] += lane->scratch_fills;
+    stats[1] += lane->scratch_fill_bytes;
+  }
+  return KSH_OK;
+}
+
+// (ctx->scan_epoch only: what ctx->scan_state holds stays as it is)
+int ksh_debug_scan_epoch(ksh_ctx* ctx, int set_to, int* current) {
+  if (!ctx) return fail(KSH_INVALID_ARGUMENT, "ctx is NULL");
+  if (set_to > 0xFFFF) return fail(KSH_INVALID_ARGUMENT, "the epoch has 16 bits");
+  if (set_to >= 0) ctx->scan_epoch = uint32_t(set_to);
+  if (current) *current = int(ctx->scan_epoch);
   return KSH_OK;
 }
 

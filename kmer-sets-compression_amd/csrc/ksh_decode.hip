@@ -855,7 +855,7 @@ int decode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_spss_view* s, int c
   decode_geometry(s, &n_words, &n_end_words, &groups, &wpg);
   const DecodeShape shape{groups, nbw, n_end_words, s->n_strings, wide};
   DecodeState st;
-  KSH_TRY(slot_layout(ctx, kSlotDecode, [&](Carver& c) { decode_layout(c, shape, &st); }));
+  KSH_TRY(slot_layout(ctx, kSlotDecode, kSlotBegin, [&](Carver& c) { decode_layout(c, shape, &st); }));
   KSH_TRY(arena_reserve(ctx, scan_scratch_bytes(s->n_strings)));
   arena_reset(ctx);
   int64_t* offw = wide ? st.coarse : d_offsets;

@@ -3812,8 +3812,8 @@ size_t encode_scratch_bytes(const ksh_geom* g, int64_t n) {
   const size_t slot = enc_slot_bytes(g, n), arena = enc_arena_bytes(g, n);
   return slot + (slot >> 3) + arena + (arena >> 2) + (size_t(2) << 20);  // (with slot_reserve's and arena_reserve's spare)
 }
-int encode_reserve(ksh_ctx* ctx, const ksh_geom* g, int64_t n) {
-  KSH_TRY(slot_reserve(ctx, kSlotEncode, enc_slot_bytes(g, n)));
+int encode_reserve(ksh_ctx* ctx, const ksh_geom* g, int64_t n, SlotUse use) {
+  KSH_TRY(slot_reserve(ctx, kSlotEncode, enc_slot_bytes(g, n), use));
   return arena_reserve(ctx, enc_arena_bytes(g, n));
 }
 
@@ -3912,7 +3912,7 @@ int encode_plan_t(ksh_ctx* ctx, const ksh_geom* g, const ksh_set_view* sv, bool 
   const int64_t nb = n_buckets(g);
   const int fine_bits = enc_fine_bits(g, n);
   const bool use_fine = fine_bits >= 2;
-  KSH_TRY(encode_reserve(ctx, g, n));
+  KSH_TRY(encode_reserve(ctx, g, n, kSlotBegin));  // (the plan begins here: the bind below finds nothing of its own)
   arena_reset(ctx);
   KSH_BOUND(layout_bind(ctx->slot[kSlotEncode], ctx->slot_bytes[kSlotEncode], [&](Carver& c) { enc_slot_layout(c, p, g, n); }));
   uint32_t* rc_cursor = reinterpret_cast<uint32_t*>(p->ctl + 1);  // k_rc_scatter_l2's per-group cursors: zeroed with the block

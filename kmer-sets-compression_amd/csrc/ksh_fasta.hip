@@ -263,7 +263,7 @@ int ksh_fasta_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t 
     p->kept_idx = c.take<int64_t>(size_t(p->n_frag + 1));
   };
   // pass 1: per-chunk arrays
-  KSH_TRY(slot_layout(ctx, kSlotText, fasta_slot));
+  KSH_TRY(slot_layout(ctx, kSlotText, kSlotBegin, fasta_slot));
   ctx->text_slot_owner = 2;
   hipLaunchKernelGGL(k_fa_newlines, dim3(fa_blocks(n_chunks, 256)), dim3(256), 0, st, p->text, n_bytes,
                      p->nl_before);
@@ -292,7 +292,7 @@ int ksh_fasta_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text, int64_t 
   // streaming passes).
   (void)layout_bytes(fasta_slot);  // (per_frag, now that the count is known)
   const bool grows = 3 * per_chunk + 3 * per_frag > ctx->slot_bytes[kSlotText];
-  KSH_TRY(slot_layout(ctx, kSlotText, fasta_slot));
+  KSH_TRY(slot_layout(ctx, kSlotText, kSlotKeep, fasta_slot));  // (the per-chunk arrays of pass 1 stay)
   if (grows) {  // a fresh buffer: the two prefix arrays are gone
     hipLaunchKernelGGL(k_fa_newlines, dim3(fa_blocks(n_chunks, 256)), dim3(256), 0, st, p->text, n_bytes,
                        p->nl_before);

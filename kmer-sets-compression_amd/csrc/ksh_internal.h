@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -133,6 +134,11 @@ struct ksh_ctx {
   // inject_min_bytes have succeeded, every further one fails; -1: off
   long long inject_skip = -1;
   size_t inject_min_bytes = 0;
+  // test hook (KSH_SCRATCH_FILL, ksh_debug_set_scratch_fill): 0..255: scratch whose contents are undefined by contract
+  // is set to this byte before it is handed out (ksh::scratch_fill); -1: off.  The counters: fills
+  // and bytes filled on this context since the value was last set (lane threads fill blocks of their parent's pool)
+  int scratch_fill = -1;
+  std::atomic<int64_t> scratch_fills{0}, scratch_fill_bytes{0};
 
   // Lanes: helper contexts on the same device, each with a stream, scratch slots and arena of its own, on
   // which independent jobs of one call run side by side with the context's own (ksh::run_on_lanes: the stale
@@ -162,6 +168,13 @@ namespace ksh {
 // out-of-memory path crashes the process: hipMalloc -> KfdDriver::AllocateMemory -> GpuAgent::Trim ->
 // AqlQueue::AsyncReclaimMainScratch, SIGSEGV)
 int device_alloc(ksh_ctx* ctx, size_t bytes, void** out);
+// The scratch fill (ksh_ctx::scratch_fill), at every point that hands out scratch with undefined contents: off, one
+// branch; on, `bytes` at p set to the byte on ctx's stream and the stream drained (the block may be used on another
+// stream next: a lane's results come from its parent's pool).
+int scratch_fill_now(ksh_ctx* ctx, void* p, size_t bytes);
+inline int scratch_fill(ksh_ctx* ctx, void* p, size_t bytes) {
+  return ctx->scratch_fill < 0 ? KSH_OK : scratch_fill_now(ctx, p, bytes);
+}
 int arena_reserve(ksh_ctx* ctx, size_t bytes);
 inline void arena_reset(ksh_ctx* ctx) { ctx->arena_used = 0; }
 // Returns nullptr when the arena is too small (callers reserve first).
@@ -183,11 +196,15 @@ int arena_layout(ksh_ctx* ctx, size_t extra, Layout&& layout) {
 }
 int plan_reserve(ksh_ctx* ctx, size_t bytes);
 enum { kSlotDecode = 0, kSlotEncode = 1, kSlotText = 2 };
-int slot_reserve(ksh_ctx* ctx, int which, size_t bytes);
+// What the caller expects to find in the slot: nothing (a plan begins to use it: its contents are undefined, and the
+// scratch fill poisons them), or the arrays it has written there (a plan that binds its arrays again, a lane that
+// maps its scratch ahead of its jobs).  A slot that has to grow loses its contents either way.
+enum SlotUse { kSlotBegin = 0, kSlotKeep = 1 };
+int slot_reserve(ksh_ctx* ctx, int which, size_t bytes, SlotUse use);
 // A slot reserved for what a layout measures, and the layout bound to it.
 template <typename Layout>
-int slot_layout(ksh_ctx* ctx, int which, Layout&& layout) {
-  KSH_TRY(slot_reserve(ctx, which, layout_bytes(layout)));
+int slot_layout(ksh_ctx* ctx, int which, SlotUse use, Layout&& layout) {
+  KSH_TRY(slot_reserve(ctx, which, layout_bytes(layout), use));
   if (!layout_bind(ctx->slot[which], ctx->slot_bytes[which], layout)) return fail(KSH_INTERNAL, "scratch arena too small");
   return KSH_OK;
 }
@@ -210,7 +227,7 @@ inline ksh_ctx* result_ctx(ksh_ctx* lane) { return lane->lane_parent ? lane->lan
 // Scratch of an SPSS encode of n k-mers (slot + arena bytes, with the reserves' spare): what a lane reserves once, at
 // its largest n (ksh_encode.hip; non-decreasing in n, so that no smaller plan on the lane maps its slot again)
 size_t encode_scratch_bytes(const ksh_geom* g, int64_t n);
-int encode_reserve(ksh_ctx* ctx, const ksh_geom* g, int64_t n);
+int encode_reserve(ksh_ctx* ctx, const ksh_geom* g, int64_t n, SlotUse use);
 
 int check_geom(const ksh_geom* g);
 int check_view(const ksh_set_view* v, const char* name);  // ksh_pair.hip

@@ -229,7 +229,7 @@ static int ensure_compacts(ksh_kss* k) {
       }
     const int rc = run_on_lanes(
         k->ctx, largest_first(stale, [&](size_t i) { return k->sets[i].n; }), encode_scratch_bytes(&k->g, n_max),
-        [&](ksh_ctx* lane) { return encode_reserve(lane, &k->g, n_max); },
+        [&](ksh_ctx* lane) { return encode_reserve(lane, &k->g, n_max, kSlotKeep); },
         [&](ksh_ctx* lane, size_t i) {
           KssCompact c;
           KSH_TRY(encode_set(lane, &k->g, k->sets[i], k->canonical, &c));
@@ -1055,7 +1055,7 @@ static int build_owned(ksh_kss* k, const ksh_spss_view* inputs, int32_t n_inputs
       if (!protocol_only && alive(k) && !mine.empty())
         poison(k, run_on_lanes(
                       ctx, largest_first(mine, [&](size_t q) { return k->sets[pd->stale[q]].n; }),
-                      encode_scratch_bytes(g, n_max), [&](ksh_ctx* lane) { return encode_reserve(lane, g, n_max); },
+                      encode_scratch_bytes(g, n_max), [&](ksh_ctx* lane) { return encode_reserve(lane, g, n_max, kSlotKeep); },
                       [&](ksh_ctx* lane, size_t q) {
                         const size_t node = pd->stale[q];
                         if (!k->sets[node].off) return int(KSH_OK);

@@ -271,7 +271,7 @@ int ksh_spss_from_text_plan(ksh_ctx* ctx, const ksh_geom* g, const char* d_text,
   KSH_TRY(arena_layout(ctx, scan_scratch_bytes(n_chunks), [&](Carver& c) { flags = c.take<int>(1); c.pad(256); }));
   hipStream_t st = ctx->stream;
   // nl_before lives in the text slot: it is needed again by ksh_spss_from_text_write
-  KSH_TRY(slot_layout(ctx, kSlotText, [&](Carver& c) { p->nl_before = c.take<int64_t>(size_t(n_chunks + 1)); }));
+  KSH_TRY(slot_layout(ctx, kSlotText, kSlotBegin, [&](Carver& c) { p->nl_before = c.take<int64_t>(size_t(n_chunks + 1)); }));
   ctx->text_slot_owner = 1;
   KSH_HIP(hipMemsetAsync(flags, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_text_count_nl, dim3(blocks_of(n_chunks, 256)), dim3(256), 0, st, p->text, n_bytes,

@@ -673,6 +673,31 @@ class Context:
         stream, 0: the default (KSH_LANES, else 4)."""
         check(lib().ksh_ctx_set_lanes(self.h, int(n)))
 
+    # test hooks (exported, not in the public header) ---------------------------------------
+    def debug_scratch_fill(self, byte):
+        """Scratch whose contents are undefined by contract is set to `byte` (0..255) before it is handed out, on this
+        context and its lanes; None or -1: off.  The counters of debug_scratch_fill_stats restart."""
+        fn = lib().ksh_debug_set_scratch_fill
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int]
+        check(fn(self.h, -1 if byte is None else int(byte)))
+
+    def debug_scratch_fill_stats(self):
+        """(fills, bytes filled) since the fill value was last set, the lanes' included."""
+        fn = lib().ksh_debug_scratch_fill_stats
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]
+        st = (C.c_int64 * 2)()
+        check(fn(self.h, st))
+        return st[0], st[1]
+
+    def debug_scan_epoch(self, set_to=None):
+        """The epoch of the context's last chained scan (csrc/ksh_scan.h); set_to: the epoch it is set to first (the
+        scan state stays as it is)."""
+        fn = lib().ksh_debug_scan_epoch
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        now = C.c_int()
+        check(fn(self.h, -1 if set_to is None else int(set_to), C.byref(now)))
+        return now.value
+
     # KmerSet::Hash / Size -------------------------------------------------------
     def set_hash(self, s):
         out = C.c_uint64()

@@ -285,22 +285,34 @@ def test_fasta_slot_growth_in_both_orders(ctx, consts):
 def svb_round_trip(ctx, name, d_in, n, want):
     """encode == reference (the size-only call too), decode(encode(v)) == v, bytes_read == size; nothing is written
     behind either output."""
-    import torch
-
     L = capi.lib()
     size = C.c_int64(-1)
     capi.check(L.ksh_svb_encode_0124(ctx.h, d_in.data_ptr(), n, None, C.byref(size)))
     assert size.value == want.size, name
+    svb_decode_guarded(ctx, name, svb_encode_guarded(ctx, name, d_in, n, want), d_in, n, want)
+
+
+def svb_encode_guarded(ctx, name, d_in, n, want):
+    """One encode into a buffer with a sentinel tail: the reference's bytes, nothing behind them.  Returns the buffer."""
+    import torch
+
     d_out = torch.full((want.size + GUARD,), SENT_B, dtype=torch.uint8, device=ctx.device)
     size = C.c_int64(-1)
-    capi.check(L.ksh_svb_encode_0124(ctx.h, d_in.data_ptr(), n, d_out.data_ptr(), C.byref(size)))
+    capi.check(capi.lib().ksh_svb_encode_0124(ctx.h, d_in.data_ptr(), n, d_out.data_ptr(), C.byref(size)))
     assert size.value == want.size, name
     host = d_out.cpu().numpy()
     assert np.array_equal(host[:want.size], want), name
     assert (host[want.size:] == SENT_B).all(), name
+    return d_out
+
+
+def svb_decode_guarded(ctx, name, d_out, d_in, n, want):
+    """One decode of an encoded buffer: the values that went in, the bytes read, nothing behind the values."""
+    import torch
+
     back = torch.full((n + 8,), SENT_L, dtype=torch.int32, device=ctx.device)
     used = C.c_int64(-1)
-    capi.check(L.ksh_svb_decode_0124(ctx.h, d_out.data_ptr(), n, back.data_ptr(), C.byref(used)))
+    capi.check(capi.lib().ksh_svb_decode_0124(ctx.h, d_out.data_ptr(), n, back.data_ptr(), C.byref(used)))
     assert used.value == want.size, name
     assert torch.equal(back[:n], d_in[:n]) and bool((back[n:] == SENT_L).all()), name
 
