@@ -34,6 +34,7 @@
 #include "ksh_seq.h"
 
 using ksh::pc::PoolBuf;
+using ksh::pc::pool_array;
 
 namespace {
 
@@ -247,18 +248,16 @@ extern "C" int ksh_link_bubbles(const ksh_link_graph* graph, ksh_ctx* ctx, int32
   // 1. the graph checked, the degrees and first targets beside it: into scratch only (the first synchronisation)
   const int64_t n_oriented = 2 * n;
   PoolBuf bad_buf(ctx), deg_buf(ctx), first_buf(ctx), flag_buf(ctx), arms_buf(ctx), rows_buf(ctx);
-  KSH_TRY(pool_alloc(ctx, 64, &bad_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(n_oriented), &deg_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(n_oriented) * 8, &first_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(n_oriented + 1) * 8, &flag_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(n_oriented + 1) * 8, &arms_buf.p));
-  if (classes) KSH_TRY(pool_alloc(ctx, size_t(graph->n_classes) * 16, &rows_buf.p));
-  auto* bad = static_cast<unsigned long long*>(bad_buf.p);
-  auto* deg = static_cast<uint8_t*>(deg_buf.p);
-  auto* first = static_cast<int64_t*>(first_buf.p);
-  auto* flag = static_cast<int64_t*>(flag_buf.p);
-  auto* arms = static_cast<int64_t*>(arms_buf.p);
-  auto* rows = static_cast<uint64_t*>(rows_buf.p);
+  unsigned long long* bad;
+  uint8_t* deg;
+  int64_t *first, *flag, *arms;
+  uint64_t* rows = nullptr;
+  KSH_TRY(pool_array(ctx, 8, &bad_buf, &bad));
+  KSH_TRY(pool_array(ctx, size_t(n_oriented), &deg_buf, &deg));
+  KSH_TRY(pool_array(ctx, size_t(n_oriented), &first_buf, &first));
+  KSH_TRY(pool_array(ctx, size_t(n_oriented + 1), &flag_buf, &flag));
+  KSH_TRY(pool_array(ctx, size_t(n_oriented + 1), &arms_buf, &arms));
+  if (classes) KSH_TRY(pool_array(ctx, size_t(graph->n_classes) * 2, &rows_buf, &rows));  // (two words a row)
   const int64_t* off = graph->d_link_offsets;
   const int64_t* to = graph->d_link_to;
   const dim3 grid(unsigned((n_oriented + kBubThreads - 1) / kBubThreads));

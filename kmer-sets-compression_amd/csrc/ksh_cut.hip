@@ -19,6 +19,7 @@
 #include "ksh_seq.h"
 
 using ksh::pc::PoolBuf;
+using ksh::pc::pool_array;
 
 namespace {
 
@@ -131,7 +132,7 @@ extern "C" int ksh_spss_cut(const ksh_spss_view* seqs, ksh_ctx* ctx, const ksh_g
   KSH_TRY(check_geom(g));
   KSH_TRY(seq_check_request(seqs, 0, 0));
   const int k = g->k;
-  if (k < 4) return fail(KSH_INVALID_ARGUMENT, "k = %d: sequence queries need K >= 4", k);
+  KSH_TRY(seq_check_k(k, ""));
   const int64_t n = seqs->n_strings;
   if (n_runs < 0) return fail(KSH_INVALID_ARGUMENT, "n_runs = %lld is negative", (long long)n_runs);
   if (n_runs < n)
@@ -139,8 +140,7 @@ extern "C" int ksh_spss_cut(const ksh_spss_view* seqs, ksh_ctx* ctx, const ksh_g
                 (long long)n);
   if (n == 0) {
     if (n_runs != 0) return fail(KSH_INVALID_ARGUMENT, "n_runs = %lld with no strings", (long long)n_runs);
-    if (seqs->n_bases != 0)
-      return fail(KSH_INVALID_ARGUMENT, "sum(lens + K) = 0 but n_bases = %lld", (long long)seqs->n_bases);
+    KSH_TRY(seq_check_empty(seqs, ""));
     if (n_bases) *n_bases = 0;
     return KSH_OK;
   }
@@ -152,12 +152,11 @@ extern "C" int ksh_spss_cut(const ksh_spss_view* seqs, ksh_ctx* ctx, const ksh_g
 
   // 1. the run list against the container's lens, and the container's own sizes: one synchronisation for both
   PoolBuf pstart_buf(ctx), bad_buf(ctx), q_buf(ctx);
-  KSH_TRY(pool_alloc(ctx, size_t(n + 1) * 8, &pstart_buf.p));
-  KSH_TRY(pool_alloc(ctx, 64, &bad_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(n_runs) * 8, &q_buf.p));
-  auto* pstart = static_cast<int64_t*>(pstart_buf.p);
-  auto* bad = static_cast<unsigned long long*>(bad_buf.p);
-  auto* q = static_cast<int64_t*>(q_buf.p);
+  int64_t *pstart, *q;
+  unsigned long long* bad;
+  KSH_TRY(pool_array(ctx, size_t(n + 1), &pstart_buf, &pstart));
+  KSH_TRY(pool_array(ctx, 8, &bad_buf, &bad));
+  KSH_TRY(pool_array(ctx, size_t(n_runs), &q_buf, &q));
   KSH_HIP(hipMemsetAsync(bad, 0xFF, 64, ctx->stream));
   hipLaunchKernelGGL(k_cut_check, dim3(unsigned((n_runs + kCutThreads - 1) / kCutThreads)), dim3(kCutThreads), 0,
                      ctx->stream, seqs->d_lens, n, d_run_offsets, d_run_start, n_runs, bad);

@@ -20,12 +20,12 @@
 //           strand bit XORed by "this end as written is not its key".
 // The result is a function of the two containers alone.
 #include "ksh_clstable.h"
-#include "ksh_kmer.h"
 #include "ksh_seq.h"
 
 #include <cstdlib>
 
 using ksh::pc::PoolBuf;
+using ksh::pc::pool_array;
 
 namespace {
 
@@ -41,15 +41,6 @@ enum { kBadNoSlot = 0, kBadLens = 1, kLocated = 2, kReportWords = 3 };
 }  // namespace
 
 namespace ksh {
-
-// The K bases from base b of the stream on (a window spans at most two words; bits behind the window never count).
-__device__ __forceinline__ uint64_t loc_window(const uint64_t* __restrict__ words, int64_t b, int k) {
-  const int64_t w = b >> 5;
-  const int o = int(b & 31);
-  uint64_t x = words[w] << (2 * o);
-  if (o + k > 32) x |= words[w + 1] >> (64 - 2 * o);  // (o >= 2 here: k <= 31)
-  return x >> (64 - 2 * k);
-}
 
 // (link_slot of ksh_links.hip: the same hash, so the tables fill alike)
 __device__ __forceinline__ uint64_t loc_slot(uint64_t key, uint64_t mask) { return pc::pc_mix(key) & mask; }
@@ -89,19 +80,17 @@ __global__ __launch_bounds__(kLocThreads) void k_loc_ends(const uint64_t* __rest
                                                           unsigned long long* __restrict__ bad) {
   const int64_t s = int64_t(blockIdx.x) * kLocThreads + threadIdx.x;
   if (s >= n_strings) return;
-  const int64_t b0 = pstart[s] + s * int64_t(k - 1);
-  const uint32_t len = lens[s];
-  const uint64_t first = loc_window(words, b0, k);
-  const uint64_t last = len == 0 ? first : loc_window(words, b0 + int64_t(len), k);
+  uint64_t first, last;
+  const bool single = seq_ends(words, lens, pstart, s, k, &first, &last);
   ends[2 * s] = first;
   ends[2 * s + 1] = last;
   loc_insert(keys, mask, loc_key(first, k, canon), s, bad);
-  if (len != 0) loc_insert(keys, mask, loc_key(last, k, canon), s, bad);
+  if (!single) loc_insert(keys, mask, loc_key(last, k, canon), s, bad);
 }
 
-// Positions i0 .. i0 + kR of the line per thread, kLocThreads * kR per workgroup; the sequence of a thread's first
-// position is searched between the sequences of the workgroup's first and last position, which two threads look up
-// among all sequences (as k_seq_extract does).
+// seq_walk over the whole line, kR positions per thread and kLocThreads * kR per workgroup: every position's key
+// looked up with plain loads (loc_find's loop, the hit's two atomics inside it: a lane that has found its slot does
+// not wait for the wave's last lane to end its probe), a hit recorded in the slot's minimum word and count.
 template <int kR>
 __global__ __launch_bounds__(kLocThreads) void k_loc_scan(const uint64_t* __restrict__ words,
                                                           const int64_t* __restrict__ pstart, int64_t n_seqs,
@@ -109,43 +98,7 @@ __global__ __launch_bounds__(kLocThreads) void k_loc_scan(const uint64_t* __rest
                                                           const unsigned long long* __restrict__ keys, uint64_t mask,
                                                           unsigned long long* __restrict__ mins,
                                                           uint32_t* __restrict__ counts) {
-  __shared__ int64_t s_range[2];
-  const int64_t blk0 = int64_t(blockIdx.x) * (kLocThreads * kR);
-  if (threadIdx.x < 2) {
-    const int64_t i = threadIdx.x == 0 ? blk0 : min(blk0 + int64_t(kLocThreads * kR), total) - 1;
-    s_range[threadIdx.x] = seq_of(pstart, 0, n_seqs - 1, i);
-  }
-  __syncthreads();
-  const int64_t i0 = blk0 + int64_t(threadIdx.x) * kR;
-  if (i0 >= total) return;
-  const int64_t i1 = min(i0 + int64_t(kR), total);
-  int64_t s = seq_of(pstart, s_range[0], s_range[1], i0);
-  int64_t s_end = pstart[s + 1];
-  const uint64_t kmask = kmer_mask(k);
-  uint64_t fwd = 0, rc = 0, cur = 0;
-  int64_t cur_w = -1;
-  bool whole = true;
-  for (int64_t p = i0; p < i1; p++) {
-    if (p >= s_end) {  // every sequence has a position: the next one starts here
-      s++;
-      s_end = pstart[s + 1];
-      whole = true;
-    }
-    const int64_t b = p + s * int64_t(k - 1);  // first base of the position's k-mer
-    if (whole) {
-      fwd = loc_window(words, b, k);
-      rc = revcomp(fwd, k);
-      whole = false;
-    } else {
-      const int64_t j = b + k - 1;  // the base that enters
-      if ((j >> 5) != cur_w) {
-        cur_w = j >> 5;
-        cur = words[cur_w];
-      }
-      const uint64_t c = (cur >> (62 - 2 * int(j & 31))) & 3;
-      fwd = ((fwd << 2) | c) & kmask;
-      rc = (rc >> 2) | ((3 - c) << (2 * (k - 1)));
-    }
+  seq_walk<kR, kLocThreads>(words, pstart, n_seqs, 0, total, k, [=](int64_t p, uint64_t fwd, uint64_t rc) {
     const uint64_t key = canon && rc < fwd ? rc : fwd;
     const unsigned long long kw = key | kValid;
     uint64_t h = loc_slot(key, mask);
@@ -159,7 +112,7 @@ __global__ __launch_bounds__(kLocThreads) void k_loc_scan(const uint64_t* __rest
         break;
       }
     }
-  }
+  });
 }
 
 __global__ __launch_bounds__(kLocThreads) void k_loc_write(const uint64_t* __restrict__ ends, int64_t n_ends, int k,
@@ -201,17 +154,6 @@ static int loc_run() {
   return r == 8 || r == 16 || r == 32 || r == 64 ? r : kLocRun;
 }
 
-// The sizes of one container checked on the device (seq_positions), the refusal prefixed with the container's name.
-static int loc_positions(ksh_ctx* ctx, const char* name, const ksh_spss_view* v, int k, int64_t* pstart,
-                         unsigned long long* bad, int64_t* total) {
-  const int rc = seq_positions(ctx, v, k, pstart, bad, total);
-  if (rc == KSH_INVALID_ARGUMENT) {
-    const std::string why = ksh_last_error();
-    return fail(rc, "%s: %s", name, why.c_str());
-  }
-  return rc;
-}
-
 }  // namespace ksh
 
 using namespace ksh;
@@ -226,21 +168,15 @@ extern "C" int ksh_seq_locate(const ksh_seq_locate_req* req) {
   if (!req->g) return fail(KSH_INVALID_ARGUMENT, "req->g is NULL");
   KSH_TRY(check_geom(req->g));
   const int k = req->g->k;
-  if (k < 4) return fail(KSH_INVALID_ARGUMENT, "req->g: k = %d: sequence queries need K >= 4", k);
+  KSH_TRY(seq_check_k(k, "req->g: "));
   const ksh_spss_view* strings = req->strings;
   const ksh_spss_view* ref = req->reference;
   if (!strings) return fail(KSH_INVALID_ARGUMENT, "req->strings is NULL");
-  if (strings->n_strings < 0 || strings->n_bases < 0)
-    return fail(KSH_INVALID_ARGUMENT, "req->strings: negative size: %lld strings, %lld bases",
-                (long long)strings->n_strings, (long long)strings->n_bases);
-  if (ref && (ref->n_strings < 0 || ref->n_bases < 0))
-    return fail(KSH_INVALID_ARGUMENT, "req->reference: negative size: %lld strings, %lld bases",
-                (long long)ref->n_strings, (long long)ref->n_bases);
+  KSH_TRY(seq_check_sizes(strings, "req->strings: "));
+  if (ref) KSH_TRY(seq_check_sizes(ref, "req->reference: "));
   const int64_t n = strings->n_strings;
   if (n == 0) {
-    if (strings->n_bases != 0)
-      return fail(KSH_INVALID_ARGUMENT, "req->strings: sum(lens + K) = 0 but n_bases = %lld",
-                  (long long)strings->n_bases);
+    KSH_TRY(seq_check_empty(strings, "req->strings: "));
     if (req->n_located) *req->n_located = 0;
     return KSH_OK;
   }
@@ -254,9 +190,7 @@ extern "C" int ksh_seq_locate(const ksh_seq_locate_req* req) {
   if (!req->d_count) return fail(KSH_INVALID_ARGUMENT, "req->d_count is NULL with %lld strings", (long long)n);
   if (n > (INT64_MAX >> 6))
     return fail(KSH_INVALID_ARGUMENT, "req->strings: n_strings = %lld is more than any device holds", (long long)n);
-  if (m == 0 && ref->n_bases != 0)
-    return fail(KSH_INVALID_ARGUMENT, "req->reference: sum(lens + K) = 0 but n_bases = %lld",
-                (long long)ref->n_bases);
+  KSH_TRY(seq_check_empty(ref, "req->reference: "));
   KSH_HIP(hipSetDevice(ctx->device));
   const int canon = req->canonical ? 1 : 0;
 
@@ -264,23 +198,20 @@ extern "C" int ksh_seq_locate(const ksh_seq_locate_req* req) {
   uint64_t slots = 1;
   while (slots < 4 * uint64_t(n)) slots <<= 1;
   PoolBuf spos_buf(ctx), rpos_buf(ctx), bad_buf(ctx), ends_buf(ctx), keys_buf(ctx), mins_buf(ctx), counts_buf(ctx);
-  KSH_TRY(pool_alloc(ctx, size_t(n + 1) * 8, &spos_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(m + 1) * 8, &rpos_buf.p));
-  KSH_TRY(pool_alloc(ctx, 64, &bad_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(2 * n) * 8, &ends_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(slots) * 8, &keys_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(slots) * 8, &mins_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(slots) * 4, &counts_buf.p));
-  auto* spos = static_cast<int64_t*>(spos_buf.p);
-  auto* rpos = static_cast<int64_t*>(rpos_buf.p);
-  auto* bad = static_cast<unsigned long long*>(bad_buf.p);
-  auto* ends = static_cast<uint64_t*>(ends_buf.p);
-  auto* keys = static_cast<unsigned long long*>(keys_buf.p);
-  auto* mins = static_cast<unsigned long long*>(mins_buf.p);
-  auto* counts = static_cast<uint32_t*>(counts_buf.p);
+  int64_t *spos, *rpos;
+  unsigned long long *bad, *keys, *mins;
+  uint64_t* ends;
+  uint32_t* counts;
+  KSH_TRY(pool_array(ctx, size_t(n + 1), &spos_buf, &spos));
+  KSH_TRY(pool_array(ctx, size_t(m + 1), &rpos_buf, &rpos));
+  KSH_TRY(pool_array(ctx, 8, &bad_buf, &bad));
+  KSH_TRY(pool_array(ctx, size_t(2 * n), &ends_buf, &ends));
+  KSH_TRY(pool_array(ctx, size_t(slots), &keys_buf, &keys));
+  KSH_TRY(pool_array(ctx, size_t(slots), &mins_buf, &mins));
+  KSH_TRY(pool_array(ctx, size_t(slots), &counts_buf, &counts));
   int64_t own = 0, total = 0;  // k-mer positions of the strings, of the reference
-  KSH_TRY(loc_positions(ctx, "req->strings", strings, k, spos, bad + kBadLens, &own));
-  if (m > 0) KSH_TRY(loc_positions(ctx, "req->reference", ref, k, rpos, bad + kBadLens, &total));
+  KSH_TRY(seq_positions(ctx, strings, k, spos, bad + kBadLens, &own, "req->strings: "));
+  if (m > 0) KSH_TRY(seq_positions(ctx, ref, k, rpos, bad + kBadLens, &total, "req->reference: "));
   if (total >= (int64_t(1) << 32))
     return fail(KSH_INVALID_ARGUMENT, "req->reference: %lld k-mer positions: the counts are exact below 2^32",
                 (long long)total);

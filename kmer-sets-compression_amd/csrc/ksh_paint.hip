@@ -202,15 +202,14 @@ extern "C" int ksh_seq_class_runs(const ksh_spss_view* seqs, ksh_kss_index* idx,
   KSH_TRY(resolve_cols(req->cols, req->n_cols, x, "req->cols", &list, &n_cols));
   KSH_TRY(class_table_check_cols(req->rows, req->n_classes, n_cols));
   const int k = x.g.k;
-  if (k < 4) return fail(KSH_INVALID_ARGUMENT, "k = %d: sequence queries need K >= 4", k);
+  KSH_TRY(seq_check_k(k, ""));
   bool identity = true;
   for (int c = 0; c < n_cols; c++) identity = identity && list.id[c] == c;
   ksh_ctx* ctx = x.ctx;
   KSH_HIP(hipSetDevice(ctx->device));
   const int64_t n = seqs->n_strings;
   if (n == 0) {
-    if (seqs->n_bases != 0)
-      return fail(KSH_INVALID_ARGUMENT, "sum(lens + K) = 0 but n_bases = %lld", (long long)seqs->n_bases);
+    KSH_TRY(seq_check_empty(seqs, ""));
     if (d_run_offsets) {  // (the one word the call writes: there before it returns, as after every other return)
       KSH_HIP(hipMemsetAsync(d_run_offsets, 0, 8, ctx->stream));
       KSH_HIP(hipStreamSynchronize(ctx->stream));
@@ -223,9 +222,9 @@ extern "C" int ksh_seq_class_runs(const ksh_spss_view* seqs, ksh_kss_index* idx,
 
   // 1. positions per sequence, scanned; the container's sizes are checked before anything reads its words
   PoolBuf pstart_buf(ctx), state_buf(ctx), pat_buf(ctx), rows_buf(ctx), cls_buf(ctx), wg_buf(ctx), tab(ctx), up(ctx);
-  KSH_TRY(pool_alloc(ctx, size_t(n + 1) * 8, &pstart_buf.p));
-  KSH_TRY(pool_alloc(ctx, 64, &state_buf.p));
-  auto* pstart = static_cast<int64_t*>(pstart_buf.p);
+  int64_t* pstart;
+  KSH_TRY(pool_array(ctx, size_t(n + 1), &pstart_buf, &pstart));
+  KSH_TRY(pool_alloc(ctx, 64, &state_buf.p));  // (a PaintState, and before it is one the word of seq_positions)
   auto* st = static_cast<PaintState*>(state_buf.p);
   int64_t total = 0;  // k-mer positions in all
   KSH_TRY(seq_positions(ctx, seqs, k, pstart, reinterpret_cast<unsigned long long*>(st), &total));
@@ -241,15 +240,14 @@ extern "C" int ksh_seq_class_runs(const ksh_spss_view* seqs, ksh_kss_index* idx,
       std::min(req->pass_positions > 0 ? req->pass_positions : seq_default_pass(12 + 8 * x.words), kSeqMaxPass);
   const int64_t cap = std::min(pass, total);
   const int64_t max_groups = (cap + kPaintThreads - 1) / kPaintThreads;
-  KSH_TRY(pool_alloc(ctx, size_t(cap) * 8, &pat_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(cap) * size_t(x.words) * 8, &rows_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(cap) * 4, &cls_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(max_groups) * 8, &wg_buf.p));
-  auto* pat = static_cast<uint64_t*>(pat_buf.p);
+  uint64_t *pat, *rows;
+  uint32_t* cls;
+  int64_t* wg;
+  KSH_TRY(pool_array(ctx, size_t(cap), &pat_buf, &pat));
+  KSH_TRY(pool_array(ctx, size_t(cap) * size_t(x.words), &rows_buf, &rows));
+  KSH_TRY(pool_array(ctx, size_t(cap), &cls_buf, &cls));
+  KSH_TRY(pool_array(ctx, size_t(max_groups), &wg_buf, &wg));
   auto* mark = static_cast<int64_t*>(pat_buf.p);  // (the patterns are done with when the marks are written)
-  auto* rows = static_cast<uint64_t*>(rows_buf.p);
-  auto* cls = static_cast<uint32_t*>(cls_buf.p);
-  auto* wg = static_cast<int64_t*>(wg_buf.p);
   KSH_HIP(hipMemsetAsync(x.d_flags, 0, 16, ctx->stream));
   uint32_t routes = total > pass ? uint32_t(KSH_QROUTE_SEQ_PASSES) : 0u;
   index_set_routes(idx, 0);

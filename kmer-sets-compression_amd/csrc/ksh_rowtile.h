@@ -45,6 +45,14 @@ struct PoolBuf {
   PoolBuf& operator=(const PoolBuf&) = delete;
 };
 
+// `count` elements of T from the context's pool into buf, *out typed on them.
+template <class T>
+int pool_array(ksh_ctx* ctx, size_t count, PoolBuf* buf, T** out) {
+  KSH_TRY(pool_alloc(ctx, count * sizeof(T), &buf->p));
+  *out = static_cast<T*>(buf->p);
+  return KSH_OK;
+}
+
 // The LDS of a walk, first in every kernel's dynamic LDS: the table (kSlots keys, 2 * kSlots row words), per node
 // the cursor and the end of its slice of the bucket, 8 words for the reductions, and n_nodes + 1 ints for the
 // tile's prefix (rounded to whole 8-byte words).  Offsets in 8-byte words; `own` is where the consumer's region

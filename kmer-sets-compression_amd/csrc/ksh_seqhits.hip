@@ -9,10 +9,13 @@
 //   3. sums the rows' columns per sequence (k_seq_count: a wave per run of positions, ballots and popcounts)
 //      into d_hits, one atomicAdd per (run of one sequence, node) with a non-zero count.
 // Patterns and rows live in the context's pool, not in its arena: the join resets the arena.
-#include "ksh_kmer.h"
+#include "ksh_rowtile.h"
 #include "ksh_seq.h"
 
 #include <algorithm>
+
+using ksh::pc::PoolBuf;
+using ksh::pc::pool_array;
 
 namespace {
 
@@ -24,17 +27,6 @@ constexpr int kCountThreads = 256;
 // The default pass: as many positions as keep the pass's patterns (8 bytes) and rows (8 W bytes) within
 // kSeqPassBytes, at most the join's own pass of 2^24 queries: 2^24 positions at W = 1, about 1.9 * 10^6 at W = 16.
 int64_t default_pass(int words) { return ksh::seq_default_pass(8 + 8 * words); }
-
-struct PoolBuf {
-  ksh_ctx* ctx;
-  void* p = nullptr;
-  explicit PoolBuf(ksh_ctx* c) : ctx(c) {}
-  ~PoolBuf() {
-    if (p) ksh::pool_free(ctx, p);  // (single stream: a later user of the block is ordered after this call's kernels)
-  }
-  PoolBuf(const PoolBuf&) = delete;
-  PoolBuf& operator=(const PoolBuf&) = delete;
-};
 
 }  // namespace
 
@@ -51,64 +43,15 @@ __global__ __launch_bounds__(256) void k_seq_sizes(const uint32_t* __restrict__ 
   if (l == 0xFFFFFFFFu) atomicMin(bad, static_cast<unsigned long long>(s));
 }
 
-// The K bases from base b of the stream on, as a 2K-bit pattern (a window spans at most two words).
-__device__ __forceinline__ uint64_t seq_window(const uint64_t* __restrict__ words, int64_t b, int k) {
-  const int64_t w = b >> 5;
-  const int o = int(b & 31);
-  uint64_t x = words[w] << (2 * o);
-  if (o + k > 32) x |= words[w + 1] >> (64 - 2 * o);  // (o >= 2 here: k <= 31)
-  return x >> (64 - 2 * k);
-}
-
-// Patterns of the pass's positions p0 .. p0 + m: thread t takes positions t * kRun .. of the pass, finds the
-// sequence of its first one (a search between the sequences of the workgroup's first and last position, which
-// two threads look up among all sequences), reads that window whole and rolls it from there: two bits in at
-// the low end, two out at the top, the reverse complement alongside.  A run that passes the end of its
-// sequence reads the next sequence's first window whole: no window crosses from one sequence into the next.
+// Patterns of the pass's positions p0 .. p0 + m: seq_walk with kRun positions per thread, the pattern of position p
+// (in canonical mode the smaller of the k-mer and its reverse complement) stored at pat[p - p0].
 __global__ __launch_bounds__(kExtractThreads) void k_seq_extract(const uint64_t* __restrict__ words,
                                                                  const int64_t* __restrict__ pstart,
                                                                  int64_t n_strings, int64_t p0, int64_t m, int k,
                                                                  int canon, uint64_t* __restrict__ pat) {
-  __shared__ int64_t s_range[2];
-  const int64_t blk0 = int64_t(blockIdx.x) * (kExtractThreads * kRun);
-  if (threadIdx.x < 2) {
-    const int64_t i = threadIdx.x == 0 ? blk0 : min(blk0 + int64_t(kExtractThreads * kRun), m) - 1;
-    s_range[threadIdx.x] = seq_of(pstart, 0, n_strings - 1, p0 + i);
-  }
-  __syncthreads();
-  const int64_t i0 = blk0 + int64_t(threadIdx.x) * kRun;
-  if (i0 >= m) return;
-  const int64_t i1 = min(i0 + int64_t(kRun), m);
-  int64_t s = seq_of(pstart, s_range[0], s_range[1], p0 + i0);
-  int64_t s_end = pstart[s + 1];
-  const uint64_t mask = kmer_mask(k);
-  uint64_t fwd = 0, rc = 0, cur = 0;
-  int64_t cur_w = -1;
-  bool whole = true;
-  for (int64_t i = i0; i < i1; i++) {
-    const int64_t p = p0 + i;
-    if (p >= s_end) {  // every sequence has a position: the next one starts here
-      s++;
-      s_end = pstart[s + 1];
-      whole = true;
-    }
-    const int64_t b = p + s * int64_t(k - 1);  // first base of the position's k-mer
-    if (whole) {
-      fwd = seq_window(words, b, k);
-      rc = revcomp(fwd, k);
-      whole = false;
-    } else {
-      const int64_t j = b + k - 1;  // the base that enters
-      if ((j >> 5) != cur_w) {
-        cur_w = j >> 5;
-        cur = words[cur_w];
-      }
-      const uint64_t c = (cur >> (62 - 2 * int(j & 31))) & 3;
-      fwd = ((fwd << 2) | c) & mask;
-      rc = (rc >> 2) | ((3 - c) << (2 * (k - 1)));
-    }
-    pat[i] = canon && rc < fwd ? rc : fwd;
-  }
+  seq_walk<kRun, kExtractThreads>(words, pstart, n_strings, p0, m, k, [=](int64_t p, uint64_t fwd, uint64_t rc) {
+    pat[p - p0] = canon && rc < fwd ? rc : fwd;
+  });
 }
 
 __device__ __forceinline__ uint64_t wave_or(uint64_t v) {
@@ -176,10 +119,26 @@ static void launch_count(hipStream_t st, const uint64_t* rows, int words, const 
                      n_strings, p0, m, n_nodes, hits);
 }
 
+int seq_check_sizes(const ksh_spss_view* v, const char* name) {
+  if (v->n_strings < 0 || v->n_bases < 0)
+    return fail(KSH_INVALID_ARGUMENT, "%snegative size: %lld strings, %lld bases", name, (long long)v->n_strings,
+                (long long)v->n_bases);
+  return KSH_OK;
+}
+
+int seq_check_k(int k, const char* name) {
+  if (k < 4) return fail(KSH_INVALID_ARGUMENT, "%sk = %d: sequence queries need K >= 4", name, k);
+  return KSH_OK;
+}
+
+int seq_check_empty(const ksh_spss_view* v, const char* name) {
+  if (v->n_strings == 0 && v->n_bases != 0)
+    return fail(KSH_INVALID_ARGUMENT, "%ssum(lens + K) = 0 but n_bases = %lld", name, (long long)v->n_bases);
+  return KSH_OK;
+}
+
 int seq_check_request(const ksh_spss_view* seqs, int route, int64_t pass_positions) {
-  if (seqs->n_strings < 0 || seqs->n_bases < 0)
-    return fail(KSH_INVALID_ARGUMENT, "negative size: %lld strings, %lld bases", (long long)seqs->n_strings,
-                (long long)seqs->n_bases);
+  KSH_TRY(seq_check_sizes(seqs, ""));
   if (pass_positions < 0)
     return fail(KSH_INVALID_ARGUMENT, "pass_positions = %lld is negative", (long long)pass_positions);
   if (route < 0 || route > 2) return fail(KSH_INVALID_ARGUMENT, "route = %d (0 auto, 1 search, 2 join)", route);
@@ -188,7 +147,7 @@ int seq_check_request(const ksh_spss_view* seqs, int route, int64_t pass_positio
 }
 
 int seq_positions(ksh_ctx* ctx, const ksh_spss_view* seqs, int k, int64_t* pstart, unsigned long long* bad,
-                  int64_t* total_out) {
+                  int64_t* total_out, const char* name) {
   const int64_t n = seqs->n_strings;
   KSH_TRY(arena_reserve(ctx, size_t(n) / 32 + (size_t(1) << 20)));  // the scan's block sums
   arena_reset(ctx);
@@ -202,11 +161,11 @@ int seq_positions(ksh_ctx* ctx, const ksh_spss_view* seqs, int k, int64_t* pstar
   KSH_HIP(hipStreamSynchronize(ctx->stream));
   const int64_t total = ctx->h_pinned[0];
   if (ctx->h_pinned[1] != -1)
-    return fail(KSH_INVALID_ARGUMENT, "lens[%lld] = UINT32_MAX: lens + 1 does not fit the container's type",
+    return fail(KSH_INVALID_ARGUMENT, "%slens[%lld] = UINT32_MAX: lens + 1 does not fit the container's type", name,
                 (long long)ctx->h_pinned[1]);
   if (total + n * int64_t(k - 1) != seqs->n_bases)
-    return fail(KSH_INVALID_ARGUMENT, "sum(lens + K) = %lld but n_bases = %lld", (long long)(total + n * int64_t(k - 1)),
-                (long long)seqs->n_bases);
+    return fail(KSH_INVALID_ARGUMENT, "%ssum(lens + K) = %lld but n_bases = %lld", name,
+                (long long)(total + n * int64_t(k - 1)), (long long)seqs->n_bases);
   *total_out = total;
   return KSH_OK;
 }
@@ -230,11 +189,10 @@ extern "C" int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int c
   KSH_TRY(seq_check_request(seqs, route, pass_positions));
   const IndexShape x = index_shape(idx);
   const int k = x.g.k;
-  if (k < 4) return fail(KSH_INVALID_ARGUMENT, "k = %d: sequence queries need K >= 4", k);
+  KSH_TRY(seq_check_k(k, ""));
   const int64_t n = seqs->n_strings;
   if (n == 0) {
-    if (seqs->n_bases != 0)
-      return fail(KSH_INVALID_ARGUMENT, "sum(lens + K) = 0 but n_bases = %lld", (long long)seqs->n_bases);
+    KSH_TRY(seq_check_empty(seqs, ""));
     index_set_routes(idx, 0);
     return KSH_OK;
   }
@@ -243,20 +201,19 @@ extern "C" int ksh_seq_hits(const ksh_spss_view* seqs, ksh_kss_index* idx, int c
 
   // 1. positions per sequence, scanned; the container's sizes are checked before anything reads its words
   PoolBuf pstart_buf(ctx), bad_buf(ctx), pat_buf(ctx), rows_buf(ctx);
-  KSH_TRY(pool_alloc(ctx, size_t(n + 1) * 8, &pstart_buf.p));
-  KSH_TRY(pool_alloc(ctx, 16, &bad_buf.p));
-  auto* pstart = static_cast<int64_t*>(pstart_buf.p);
-  auto* bad = static_cast<unsigned long long*>(bad_buf.p);
+  int64_t* pstart;
+  unsigned long long* bad;
+  KSH_TRY(pool_array(ctx, size_t(n + 1), &pstart_buf, &pstart));
+  KSH_TRY(pool_array(ctx, 2, &bad_buf, &bad));
   int64_t total = 0;  // k-mer positions in all
   KSH_TRY(seq_positions(ctx, seqs, k, pstart, bad, &total));
 
   // 2. the passes
   const int64_t pass = std::min(pass_positions > 0 ? pass_positions : default_pass(x.words), kSeqMaxPass);
   const int64_t cap = std::min(pass, total);
-  KSH_TRY(pool_alloc(ctx, size_t(cap) * 8, &pat_buf.p));
-  KSH_TRY(pool_alloc(ctx, size_t(cap) * size_t(x.words) * 8, &rows_buf.p));
-  auto* pat = static_cast<uint64_t*>(pat_buf.p);
-  auto* rows = static_cast<uint64_t*>(rows_buf.p);
+  uint64_t *pat, *rows;
+  KSH_TRY(pool_array(ctx, size_t(cap), &pat_buf, &pat));
+  KSH_TRY(pool_array(ctx, size_t(cap) * size_t(x.words), &rows_buf, &rows));
   KSH_HIP(hipMemsetAsync(d_hits, 0, size_t(n) * size_t(x.n_nodes) * 4, ctx->stream));
   KSH_HIP(hipMemsetAsync(x.d_flags, 0, 16, ctx->stream));
   uint32_t routes = total > pass ? uint32_t(KSH_QROUTE_SEQ_PASSES) : 0u;
